@@ -15,7 +15,19 @@ Inputs are resident in HBM before the timed region.  value = proposals of
 all ranks / max-over-ranks wall time (weak scaling: one chain per GPU,
 independent chains, no data-path collective).
 
-Also reported:
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the
+headline needs: set up, W warm-up steps, the N timed steps, the result line
+(with `ms_per_step` and the roofline block of the timed region's own launches).
+`--dump-outputs DIR` then also writes what the timed path left after its last
+step, as DIR/<name>.npy (float64): the chain's model (xCell, yCell, zCell,
+zeta), its ptS and phi, and its counters -- what a caller of td_chain_run reads
+back through td_chain_get_model / td_chain_stats_get.  Models and seeds are
+fixed, so the same arguments give the same inputs in every run and two builds
+can be compared array for array.  Everything below takes runs of its own and is
+measured only with `--full`.
+
+Reported with --full (the `roofline` block itself is in every line; its
+`latency` phase stamps are a stamped run after the timed region):
   roofline      -- k_chain_run (the only kernel in the timed region).  Its
                    bound is LATENCY (one persistent workgroup per chain: a
                    chain of dependent barriers and LDS/L2 round trips per
@@ -160,6 +172,32 @@ def phase_cycles(tt, ch, iters):
             "note": "stamped run (+~5 %), after the timed region; per-phase cycles are the latency yardstick"}
 
 
+DUMP_LIMIT_BYTES = 64e6  # of one run's --dump-outputs, over all ranks
+
+
+def dump_outputs(d, chains, rank, world):
+    """--dump-outputs: the state the timed path left after its last step, as a
+    caller reads it back (td_chain_get_model, td_chain_stats_get): per chain
+    xCell, yCell, zCell, zeta, ptS, phi (1 value) and counters (iterations,
+    ncells, accepted x 4, proposed x 4: birth/death/change/move), float64
+    .npy.  One chain on one rank: DIR/<name>.npy; otherwise
+    DIR/rank<r>_chain<j>_<name>.npy for the rank's first chains, as many as fit
+    its share of DUMP_LIMIT_BYTES (the same ones in every run)."""
+    os.makedirs(d, exist_ok=True)
+    room = DUMP_LIMIT_BYTES / world
+    for j, ch in enumerate(chains):
+        m, st = ch.model(), ch.stats()
+        arrs = {"xCell": m.xCell, "yCell": m.yCell, "zCell": m.zCell, "zeta": m.zeta, "ptS": m.ptS,
+                "phi": [st["phi"]], "counters": [st["iterations"], st["ncells"]] + st["accepted"] + st["proposed"]}
+        arrs = {k: np.asarray(v, dtype=np.float64) for k, v in arrs.items()}
+        room -= sum(v.nbytes + 128 for v in arrs.values())  # (+ the .npy header)
+        if room < 0:
+            break
+        pre = "" if world == 1 and len(chains) == 1 else "rank%d_chain%d_" % (rank, j)
+        for k, v in arrs.items():
+            np.save(os.path.join(d, pre + k + ".npy"), v)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -167,6 +205,13 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--cells", type=int, default=5000)
     ap.add_argument("--iters-per-step", type=int, default=5000)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline (phase stamps, "
+                         "full_evaluate, dropin, stress, config 4, posterior maps, trilinear, many chains, the CPU "
+                         "baseline; at N > 1 the multi-rank legs); the --no-* options below choose among these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path left after its last step (each chain's "
+                         "model, ptS, phi and counters) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-full-evaluate", action="store_true")
@@ -391,6 +436,8 @@ def main():
     s1["ncells"] = chains[0].stats()["ncells"]
     launches, kms = ctx.timing(kernel="chain_run")
     ctx.timing(enable=False)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, chains, rank, world)
     if dist is not None:
         import torch
 
@@ -436,11 +483,22 @@ def main():
                                    C == 1 and ladder is None and N == 5000 and a.iters_per_step == 5000,
                                    headline=True),
     }
-    if C == 1 and ladder is None and not a.no_phases:  # the latency yardstick, measured after the timed region
+    if a.full and C == 1 and ladder is None and not a.no_phases:  # the latency yardstick, after the timed region
         out["roofline"]["latency"] = phase_cycles(tt, chains[0], min(a.iters_per_step, 5000))
     if ladder is not None:
         out["tempering"] = {"replicas": ladder.R, "temps": [round(t, 4) for t in ladder.temps],
                             "swap_rates": [round(r, 3) for r in ladder.swap_rates()]}
+
+    def finish():
+        for c in chains:
+            c.close()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+
+    if not a.full:  # a plain run ends here: everything below takes runs of its own
+        return finish()
     legs = []  # the multi-rank legs, each under a deadline (run_leg): the headline above is already measured
     if dist is not None and a.config4:  # every rank: config 4, one tempered replica per rank, RCCL allgather
         legs.append(("config4_ranks", lambda: config4_ranks(tt, ds, dist, coll_dev, rank, world, local,
@@ -478,12 +536,7 @@ def main():
             if key in aux and key in out and out[key][unit] > 0:
                 out[key]["cpu_baseline"] = aux[key]
                 out[key]["speedup_vs_cpu_baseline"] = round(aux[key][unit] / out[key][unit], 1)
-    for c in chains:
-        c.close()
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if dist is not None:
-        dist.destroy_process_group()
+    finish()
 
 
 def ladder_modes(tt, device):

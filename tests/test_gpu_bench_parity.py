@@ -93,6 +93,49 @@ def test_config3_headline_run_follows_host(tt, ds, ctx, orc):
     host.close()
 
 
+@pytest.mark.timeout(120)
+def test_plain_run_dumps_the_timed_chain(tt, ds, ctx, tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W --dump-outputs DIR` prints
+    the headline line alone (nothing that takes a run of its own: those need
+    --full) and writes the timed chain's state after its last step: equal, bit
+    for bit, to the same chain (model seed 3, chain seed 1000) run here over
+    the same (W + N) launches."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warm, iters = 3, 1, 300
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+                        str(warm), "--iters-per-step", str(iters), "--dump-outputs", str(tmp_path / "dump")],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=100, cwd=root)
+    assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
+    lines = [x for x in p.stdout.decode().splitlines() if x.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == steps and out["warmup"] == warm and out["value"] > 0 and out["ms_per_step"] > 0
+    assert out["value"] == pytest.approx(iters / out["ms_per_step"] * 1e3, rel=1e-3)
+    assert out["roofline"]["bound"] == "latency" and "latency" not in out["roofline"]
+    for k in ("full_evaluate", "dropin", "stress", "config4_tempering", "exchange_cost", "posterior_maps",
+              "ingest_trilinear", "many_chains", "many_chains_2per_cu", "cpu_baseline"):
+        assert k not in out, k
+    prm = tt.define_TDstructrure().replace(max_cells=2 * 5000)
+    ch = tt.Chain(ctx, tt.chain_params(prm, ds, seed=1000, chain=1), tt.random_model(5000, 3))
+    for _ in range(warm + steps):
+        ch.run(iters)
+    m, st = ch.model(), ch.stats()
+    got = {f[:-4]: np.load(tmp_path / "dump" / f) for f in sorted(os.listdir(tmp_path / "dump"))}
+    assert sorted(got) == ["counters", "phi", "ptS", "xCell", "yCell", "zCell", "zeta"]
+    assert all(v.dtype == np.float64 for v in got.values())
+    for k in ("xCell", "yCell", "zCell", "zeta", "ptS"):
+        assert np.array_equal(got[k], getattr(m, k)), k
+    assert got["phi"].tolist() == [st["phi"]]
+    assert got["counters"].tolist() == [st["iterations"], st["ncells"]] + st["accepted"] + st["proposed"]
+    assert got["counters"][0] == (warm + steps) * iters  # --steps set the number of timed steps
+    ch.close()
+
+
 @pytest.mark.timeout(600)
 def test_many_chains_batch_follows_solo_and_host(tt, ds, ctx, orc):
     prm = tt.define_TDstructrure().replace(max_cells=2 * 5000)

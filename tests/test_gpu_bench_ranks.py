@@ -32,7 +32,7 @@ def test_bench_two_ranks_gloo(launcher):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     pre = ([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
             "127.0.0.1", "--master-port", str(port)] if launcher == "torchrun" else [sys.executable])
-    cmd = pre + [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1",
+    cmd = pre + [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--full",
            "--warmup", "0", "--iters-per-step", "500", "--no-cpu-baseline", "--no-full-evaluate", "--no-dropin",
            "--batch-chains", "0", "--config4-rounds", "40", "--stress-iters", "100", "--no-phases"]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=400, cwd=ROOT)
@@ -69,7 +69,7 @@ def test_bench_stalled_leg_prints_headline():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(TD_BENCH_BACKEND="gloo", TD_BENCH_DEVICE="0", TD_BENCH_STALL_LEG="config4_ranks:1")
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--full",
            "--iters-per-step", "500", "--no-cpu-baseline", "--no-full-evaluate", "--no-dropin", "--batch-chains", "0",
            "--config4-rounds", "40", "--stress-iters", "100", "--no-phases", "--leg-deadline", "20"]
     t0 = time.time()

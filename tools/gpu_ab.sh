@@ -4,7 +4,7 @@
 set -o pipefail
 out=gpurun_out/$1; shift
 mkdir -p $out
-A="--steps 10 --warmup 2 --no-cpu-baseline --no-full-evaluate --no-dropin --no-config4 --no-stress --batch-chains 0"
+A="--full --steps 10 --warmup 2 --no-cpu-baseline --no-full-evaluate --no-dropin --no-config4 --no-stress --batch-chains 0"
 for k in 1 2; do
   for nv in "$@"; do
     v=${nv%%=*}; lib=${nv#*=}

@@ -3,7 +3,7 @@
 set -o pipefail
 out=gpurun_out/$1; shift
 mkdir -p $out
-A="--steps 2 --warmup 1 --no-cpu-baseline --no-full-evaluate --no-dropin --no-config4 --no-stress --no-phases"
+A="--full --steps 2 --warmup 1 --no-cpu-baseline --no-full-evaluate --no-dropin --no-config4 --no-stress --no-phases"
 for k in 1 2; do
   for nv in "$@"; do
     v=${nv%%=*}; lib=${nv#*=}

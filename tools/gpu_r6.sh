@@ -14,7 +14,7 @@ echo "tests rc=$rc: $(tail -1 $out/tests.log)"
 [ $rc -ne 0 ] && { grep -E "FAILED|Error|Timeout" $out/tests.log | head -20; exit 1; }
 fi
 unset TD_LIB_PATH
-A="--steps 10 --warmup 2 --no-cpu-baseline --no-full-evaluate --no-dropin --no-config4 --no-stress --batch-chains 0"
+A="--full --steps 10 --warmup 2 --no-cpu-baseline --no-full-evaluate --no-dropin --no-config4 --no-stress --batch-chains 0"
 for k in 1 2; do
   for nv in "$@"; do
     v=${nv%%=*}; lib=${nv#*=}

@@ -7,7 +7,7 @@ TAG=${1:-aux}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$TAG/aux
 mkdir -p $OUT
-A="--steps 1 --warmup 0 --no-cpu-baseline --no-dropin --no-config4 --no-stress --batch-chains 0"
+A="--full --steps 1 --warmup 0 --no-cpu-baseline --no-dropin --no-config4 --no-stress --batch-chains 0"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py $A > $OUT/trace.log 2>&1 || exit 1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o run -- python3 bench.py $A > $OUT/fetch.log 2>&1 || exit 1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o run -- python3 bench.py $A > $OUT/write.log 2>&1 || exit 1
