@@ -259,6 +259,73 @@ int td_chain_get_model(const td_chain *ch, double *xCell, double *yCell, double 
 int td_chain_set_temperature(td_chain *ch, double temperature);
 
 /* ------------------------------------------------------------------------
+ * Sample history -- the thinned model_hist of TD_inversion_function.jl:275-288
+ * (every keep_each-th model from burn_in on), recorded in DEVICE memory while
+ * the chain runs, so a whole thinned run is one launch instead of one launch
+ * and one td_chain_get_model per saved model.
+ *   Layout: the cells of the samples packed one after the other in four SoA
+ * component arrays (x, y, z, zeta) of one stride = max_cells_total, each
+ * sample's cells in Julia order; a device-resident prefix off[max_samples + 1]
+ * (off[0] = 0) holds the samples' cell offsets -- the (cell_off, cells,
+ * stride) form the posterior kernels take.  Per sample a header: the absolute
+ * iteration index (the value ChainScalars::iter counts: a chain started at
+ * start_iter = 1 saves the model after its i-th iteration with iteration i),
+ * the exact phi, ncells and Model.action / Model.accept of that iteration
+ * (TD_inversion_function.jl:73-74); with_ptS != 0 also ptS, [max_samples][n].
+ * The per-action counters are not part of a sample: when the DEVICE engine
+ * takes it the next proposal is already drawn and counted.
+ *   td_history_create checks its arguments before any HIP call: max_samples
+ * < 1, max_cells_total < 1 or a NULL context give TD_ERR_ARG and a message
+ * (td_last_error(NULL) without a context).  td_history_clear empties the
+ * history (its capacity stays).  A history belongs to its context and must be
+ * destroyed before it.
+ *   td_history_read: ONE bulk read of samples [first, first + count): off_out
+ * [count + 1] rebased to 0; x / y / z / zeta of capacity cell_cap (TD_ERR_ARG
+ * when the samples hold more cells); phi, iter, action, accept [count];
+ * ptS_out [count x n] (nullable; TD_ERR_ARG if the history has no ptS).  Any
+ * output may be NULL.
+ * ------------------------------------------------------------------------ */
+typedef struct td_history td_history;
+int td_history_create(td_history **out, td_ctx *ctx, int64_t max_samples, int64_t max_cells_total, int with_ptS);
+int td_history_destroy(td_history *h);
+int td_history_clear(td_history *h);
+int td_history_count(const td_history *h, int64_t *samples, int64_t *cells_used);
+int td_history_read(td_history *h, int64_t first, int64_t count, int64_t *off_out, double *x, double *y, double *z,
+                    double *zeta, int64_t cell_cap, double *phi, int64_t *iter, int32_t *action, int32_t *accept,
+                    double *ptS_out);
+/* td_chain_run(ch, iterations), with the model after the call's iterations
+ * number first, first + every, ... (1-based; first >= 1, every >= 1; those
+ * <= iterations) appended to h: the DEVICE engine's kernel writes them as it
+ * goes (one launch, no host in the loop); HOST and DROPIN append from their
+ * host loop (the parity twins).  The chain's trajectory, stats and end state
+ * are those of the unrecorded run, and a run split over several calls (first
+ * carried over) leaves the same history as one call.
+ *   Capacity is checked on the host BEFORE anything runs: with new = the
+ * number of samples the call takes, samples + new <= max_samples and
+ * cells_used + new * (the chain's max_cells) <= max_cells_total; otherwise
+ * TD_ERR_ARG with a message, nothing has run, chain and history are unchanged.
+ * Nothing is ever truncated.  A history accumulates across calls (and across
+ * chains of its context, one after the other).
+ *   td_chain_run_batch_recorded: td_chain_run_batch with one history per chain
+ * (hs[k] for chains[k]), in one launch -- the packed two-chains-per-CU kernels
+ * included; a history listed twice is TD_ERR_ARG.
+ *   A chain held by a running td_rounds launch is stopped first, as by every
+ * other call.  Recording inside td_rounds_run / _temper / _exchange and in
+ * td_evaluate's resident server is not provided. */
+int td_chain_run_recorded(td_chain *ch, int64_t iterations, int64_t first, int64_t every, td_history *h);
+int td_chain_run_batch_recorded(td_chain *const *chains, int64_t nchains, int64_t iterations, int64_t first,
+                                int64_t every, td_history *const *hs);
+/* td_rasterize on the concatenation of the histories' samples, history by
+ * history in sample order (model_hist order, MCsub.jl:761-763), bit-identical
+ * to td_rasterize on the models read back.  The cells reach the kernels by
+ * device-to-device copies; only the offsets come from the histories' host
+ * mirror.  (Where td_rasterize would take its per-model search, whose
+ * bounding boxes are computed on the host, the cells are fetched and that
+ * path runs.)  Every history must belong to ctx and hold >= 1 sample in all. */
+int td_history_rasterize(td_ctx *ctx, td_history *const *hs, int64_t nh, const double *qx, const double *qy,
+                         const double *qz, int64_t nq, double *mean_out, double *std_out, double *values_out);
+
+/* ------------------------------------------------------------------------
  * Resident tempering rounds (parallel tempering; the reference's
  * chains are independent pmap workers, main_inversion.jl:15, so this is a new
  * capability): DEVICE chains of one context run in ONE launch that stays

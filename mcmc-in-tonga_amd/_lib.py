@@ -85,6 +85,16 @@ SIGNATURES = {
     "td_chain_stats_get": (ctypes.c_int, [_vp, ctypes.POINTER(TdChainStats)]),
     "td_chain_get_model": (ctypes.c_int, [_vp, _pd, _pd, _pd, _pd, _i64, _pi64, _pd, _pd]),
     "td_chain_set_temperature": (ctypes.c_int, [_vp, _d]),
+    "td_history_create": (ctypes.c_int, [ctypes.POINTER(_vp), _vp, _i64, _i64, ctypes.c_int]),
+    "td_history_destroy": (ctypes.c_int, [_vp]),
+    "td_history_clear": (ctypes.c_int, [_vp]),
+    "td_history_count": (ctypes.c_int, [_vp, _pi64, _pi64]),
+    "td_history_read": (ctypes.c_int, [_vp, _i64, _i64, _pi64, _pd, _pd, _pd, _pd, _i64, _pd, _pi64, _pi32, _pi32,
+                                       _pd]),
+    "td_chain_run_recorded": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp]),
+    "td_chain_run_batch_recorded": (ctypes.c_int, [ctypes.POINTER(_vp), _i64, _i64, _i64, _i64,
+                                                   ctypes.POINTER(_vp)]),
+    "td_history_rasterize": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, _pd, _pd, _pd, _i64, _pd, _pd, _pd]),
     # include/tdstar_testing.h
     "tdt_philox": (None, [_pu32, _pu32, _pu32]),
     "tdt_det_log": (_d, [_d]),

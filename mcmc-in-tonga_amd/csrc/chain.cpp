@@ -28,6 +28,7 @@
 #include "chain_logic.h"
 #include "comm.h"
 #include "ctx.h"
+#include "history.h"
 
 using namespace tdstar;
 
@@ -1418,6 +1419,123 @@ int td_chain_run_batch(td_chain *const *chains, int64_t nchains, int64_t iterati
     for (int64_t b = 0; b < nchains; ++b) {
         adopt_scalars(chains[b]);
         chains[b]->stats.iterations += iterations;
+    }
+    return TD_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the most cells a sample of this chain can hold: births stop at max_cells (a starting model above it only shrinks)
+int64_t sample_cells_bound(const td_chain *ch) {
+    return std::max<int64_t>((int64_t)ch->prm.max_cells, ch->stats.ncells);
+}
+
+int recorded_args(td_ctx *c, int64_t iterations, int64_t first, int64_t every, const char *who) {
+    if (iterations < 0 || first < 1 || every < 1)
+        return set_err(c, TD_ERR_ARG, std::string(who) + ": need iterations >= 0, first >= 1, every >= 1");
+    return TD_OK;
+}
+
+// this launch's recording into the chain's descriptor (every == 0: off again)
+void set_recording(td_chain *ch, const td_history *h, int64_t first, int64_t every) {
+    RecDesc r{};
+    if (h) {
+        r = h->d;
+        r.base = (long long)h->samples;
+        r.first = (long long)first;
+        r.every = (long long)every;
+    }
+    ch->dev.rec = r;
+    ch->desc_dirty = true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int td_chain_run_recorded(td_chain *ch, int64_t iterations, int64_t first, int64_t every, td_history *h) {
+    if (!ch || !h) return chain_err(ch, TD_ERR_ARG, "td_chain_run_recorded: NULL argument");
+    td_ctx *c = ch->ctx;
+    if (h->ctx != c) return set_err(c, TD_ERR_ARG, "td_chain_run_recorded: the history belongs to another context");
+    int rc = recorded_args(c, iterations, first, every, "td_chain_run_recorded");
+    if (rc) return rc;
+    if (ch->rounds && ch->rounds->running) {  // (its cell count is the launch's until it returns)
+        rc = rounds_stop(ch->rounds);
+        if (rc) return rc;
+    }
+    const int64_t added = history_new_samples(iterations, first, every);
+    rc = history_check_room(h, added, sample_cells_bound(ch), "td_chain_run_recorded");
+    if (rc) return rc;
+    if (added == 0) return td_chain_run(ch, iterations);
+    if (ch->engine != TD_ENGINE_DEVICE) {  // the parity twins: appended from the host loop
+        int64_t done = 0;
+        for (int64_t k = 0; k < added; ++k) {
+            const int64_t upto = first + k * every;
+            rc = td_chain_run(ch, upto - done);
+            if (rc) return rc;
+            done = upto;
+            servers_quiesce(nullptr);  // (DROPIN's resident td_evaluate server: no copy waits behind it)
+            rc = history_append_host(h, ch->x.data(), ch->y.data(), ch->z.data(), ch->zeta.data(),
+                                     (int64_t)ch->x.size(), ch->phi, ch->iter - 1, ch->stats.last_action,
+                                     ch->stats.last_accept, ch->ptS.data());
+            if (rc) return rc;
+        }
+        return td_chain_run(ch, iterations - done);
+    }
+    set_recording(ch, h, first, every);
+    rc = td_chain_run(ch, iterations);
+    set_recording(ch, nullptr, 0, 0);
+    if (rc) return rc;
+    return history_adopt(h, added);
+}
+
+int td_chain_run_batch_recorded(td_chain *const *chains, int64_t nchains, int64_t iterations, int64_t first,
+                                int64_t every, td_history *const *hs) {
+    if (!chains || !hs || nchains <= 0 || nchains > INT32_MAX) return TD_ERR_ARG;
+    td_ctx *c = chains[0] ? chains[0]->ctx : nullptr;
+    if (!c) return TD_ERR_ARG;
+    int rc = recorded_args(c, iterations, first, every, "td_chain_run_batch_recorded");
+    if (rc) return rc;
+    bool host = false;
+    for (int64_t b = 0; b < nchains; ++b) {
+        if (!chains[b] || chains[b]->ctx != c || !hs[b] || hs[b]->ctx != c)
+            return set_err(c, TD_ERR_ARG,
+                           "td_chain_run_batch_recorded: every chain and history must be non-NULL and share one context");
+        host |= chains[b]->engine != TD_ENGINE_DEVICE;
+        for (int64_t k = 0; k < b; ++k) {
+            if (chains[k] == chains[b])
+                return set_err(c, TD_ERR_ARG, "td_chain_run_batch_recorded: a chain appears twice");
+            if (hs[k] == hs[b])
+                return set_err(c, TD_ERR_ARG, "td_chain_run_batch_recorded: a history appears twice");
+        }
+    }
+    for (int64_t b = 0; b < nchains; ++b)
+        if (chains[b]->rounds && chains[b]->rounds->running) {
+            rc = rounds_stop(chains[b]->rounds);
+            if (rc) return rc;
+        }
+    const int64_t added = history_new_samples(iterations, first, every);
+    for (int64_t b = 0; b < nchains; ++b) {
+        rc = history_check_room(hs[b], added, sample_cells_bound(chains[b]), "td_chain_run_batch_recorded");
+        if (rc) return rc;
+    }
+    if (added == 0) return td_chain_run_batch(chains, nchains, iterations);
+    if (host || nchains == 1) {
+        for (int64_t b = 0; b < nchains; ++b) {
+            rc = td_chain_run_recorded(chains[b], iterations, first, every, hs[b]);
+            if (rc) return rc;
+        }
+        return TD_OK;
+    }
+    for (int64_t b = 0; b < nchains; ++b) set_recording(chains[b], hs[b], first, every);
+    rc = td_chain_run_batch(chains, nchains, iterations);  // (the launch takes the descriptors as they are now)
+    for (int64_t b = 0; b < nchains; ++b) set_recording(chains[b], nullptr, 0, 0);
+    if (rc) return rc;
+    for (int64_t b = 0; b < nchains; ++b) {
+        rc = history_adopt(hs[b], added);
+        if (rc) return rc;
     }
     return TD_OK;
 }

@@ -80,6 +80,24 @@ struct ScriptStep {
 };
 constexpr int kMaxScript = 2;
 
+// Recording (td_chain_run_recorded, history.h): where a launch writes the model after its iterations
+// number first, first + every, ... (1-based).  The buffers are a td_history's (device memory): the
+// samples' cells packed one after the other in four SoA arrays of one stride, in Julia order, with the
+// prefix off[] of their offsets (off[base] is in place when the launch starts; sample k writes
+// off[k + 1]); a header per sample; ptS rows when the history keeps them.  The host has checked the
+// capacity for every sample of the launch: the kernel never tests for an overflow.
+struct RecDesc {
+    double *cells;     // [4][stride]: x, y, z, zeta
+    long long stride;
+    long long *off;    // [max_samples + 1]
+    long long *iter;   // [max_samples] the absolute index of the iteration the sample follows
+    double *phi;       // [max_samples] exact
+    int *ncells, *action, *accept;  // [max_samples]
+    double *ptS;       // [max_samples][n], or null
+    long long base;    // the index of the launch's first sample
+    long long first, every;  // every == 0: recording off
+};
+
 struct DevChain {
     // geometry (owned by the td_ctx)
     const double *px, *py, *pz, *w, *tS, *sig;
@@ -127,6 +145,7 @@ struct DevChain {
     CellEntry *buckets;     // [G * kBucketCap] a cell's site and value, inline: a grid search reads no cell array
     int *bslot;             // [G * kBucketCap] the entry's slot
     int *grid_overflow;     // sticky: a bucket overflowed -> always scan all cells
+    RecDesc rec;            // this launch's recording (free-running launches; every == 0: none)
 };
 
 // Scripted launches (n > 0: iteration k runs step[k] instead of a draw; no

@@ -1291,18 +1291,80 @@ __device__ void server_report(double *outp, const Views &v, const Shared &sh, in
     }
 }
 
+// One sample of a recorded launch (RecDesc, chain_dev.h), by the whole block right after the
+// iteration-end barrier: the model of the iteration just finished is complete there -- the cells by
+// slot in HBM (tid 0, phase G), ptS committed (all threads, phase G), the Julia order shifted or
+// appended (phase G; the LDS layout's shifting waves are past the barrier too), and sh.phi exact (wave
+// 0 made it so before the barrier).  The cells are gathered through the order into the history's packed
+// arrays by the whole block, U = 4 cells (16 loads) in flight per thread: 5000 cells are three rounds
+// of 512 threads, where one wave alone would need twenty.  (The unroll hardly matters: the copy takes
+// 15.6-17k cycles at 5000 cells with U = 1, 2 or 4, and 21k with 8 -- 40000 8-byte accesses through
+// one CU's memory pipeline, not a latency chain)  Then ptS; tid 0 writes the header and the
+// next sample's offset.  The caller's barrier follows before phase G of a later iteration can change
+// what is read here.  Out of line, the arrays by value (as exact_sums): the
+// kernel is at its register limit.
+__device__ __attribute__((noinline)) void record_sample(const DevChain &d, const int *ord, const double *ptS,
+                                                        const Shared &sh, long long it, long long iter0, int action,
+                                                        int accept, int tid, int nth) {
+    const RecDesc &rc = d.rec;
+    const int nc = sh.ncells, n = d.n;
+    const long long k = rc.base + (it + 1 - rc.first) / rc.every, iter = iter0 + it;  // (one division per sample)
+    // (written by tid 0 at the previous sample, before a block barrier: a plain vector load)
+    const long long o = __hip_atomic_load(rc.off + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    double *ox = rc.cells + o, *oy = ox + rc.stride, *oz = oy + rc.stride, *oze = oz + rc.stride;
+    const double *cx = d.cx, *cy = d.cy, *cz = d.cz, *cze = d.czeta;
+    constexpr int U = 4;
+    for (int j0 = tid; j0 < nc; j0 += U * nth) {
+        int s[U];
+        double x[U], y[U], z[U], ze[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) s[u] = ord[min(j0 + u * nth, nc - 1)];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            x[u] = gload(cx + s[u]);
+            y[u] = gload(cy + s[u]);
+            z[u] = gload(cz + s[u]);
+            ze[u] = gload(cze + s[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * nth;
+            if (j < nc) {
+                gstore(ox + j, x[u]);
+                gstore(oy + j, y[u]);
+                gstore(oz + j, z[u]);
+                gstore(oze + j, ze[u]);
+            }
+        }
+    }
+    if (rc.ptS) {
+        double *op = rc.ptS + k * n;
+        for (int r = tid; r < n; r += nth) gstore(op + r, ptS[r]);
+    }
+    if (tid == 0) {
+        rc.iter[k] = iter;
+        rc.phi[k] = sh.phi;
+        rc.ncells[k] = nc;
+        rc.action[k] = action;
+        rc.accept[k] = accept;
+        rc.off[k + 1] = o + nc;
+    }
+}
+
 // SCRIPT: host-given proposals (td_evaluate's incremental path: scripted
 // steps, the resident server); a free-running chain's instance has none of
 // that code on its path.
 // SMALL: the tiles mirrored in LDS (else in HBM, with super-tiles); RLDS: the per-ray arrays and the
 // Julia order mirrored too (the 381-ray configs, 8 waves); NTH: 512 threads, or 256 (two chains per CU)
-template <bool SMALL, bool SCRIPT, int NTH, bool RLDS = SMALL, bool ROUNDS = false>
+// REC: a recorded launch (RecDesc): the instances without it carry none of its code
+template <bool SMALL, bool SCRIPT, int NTH, bool RLDS = SMALL, bool ROUNDS = false, bool REC = false>
 __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict__ dptr, long long iters,
                                                              ScriptArgs sa) {
     constexpr bool WALK = !SMALL || kSmallWalk;  // chi^2 by the event walk
     constexpr bool kNoBarB = RLDS && !SCRIPT;     // phase B may end without a block barrier (below)
     constexpr int kWv = NTH / 64;  // waves: 8 (one chain per CU), or 4 (rays in HBM: two chains per CU)
     static_assert(!RLDS || SMALL, "rays in LDS only with the tiles in LDS");
+    static_assert(!REC || (!SCRIPT && !ROUNDS), "recording: free-running chains outside tempering rounds");
     static_assert(NTH == kChainThreads || (!RLDS && !SCRIPT && NTH == kChainThreads / 2),
                   "512 threads, or 256 with the rays in HBM");
     if (sa.pin >= 0) {  // one chain, launched as 8 workgroups: only the one on XCD `pin` runs it
@@ -1548,6 +1610,10 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
     bool pend_sup = false;  // rays in HBM: its super-tiles' maxima not yet refreshed
     int last_action = 0, last_accept = 0;  // tid 0: Model.action / accept of the last iteration
     long long it_done = 0;                 // iterations run (server mode: until QUIT)
+    // recording (RecDesc): the launch's next sampled iteration, 1-based (block-uniform; never, when off)
+    long long rec_next = LLONG_MAX;
+    if constexpr (REC)
+        if (d.rec.every > 0 && !rbx) rec_next = d.rec.first;
     // LDS layout, decisions on bounds (phase F): a proposal accepted on bounds of phi_n leaves its
     // chi^2 partial sums unformed -- prefix[] stays exact below ex_upto only (wave 0), and tid 0
     // keeps phi_r as an estimate inside [phi_lo, phi_hi].  They are made exact again by the next
@@ -2353,6 +2419,8 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
                             // a tempering round's last iteration publishes phi: decided exactly (and
                             // every sum made exact) whatever the bounds say (testing: every k-th too)
                             if ((rbx || xch) && it + 1 == round_end) bdec = 0;
+                            if constexpr (REC)
+                                if (it + 1 == rec_next) bdec = 0;  // a recorded sample carries the exact phi: likewise
                             if (d.exact_every > 0 && (it % d.exact_every) == d.exact_every - 1) bdec = 0;
                             exact = bdec == 0;
                             phi_n = Sa;  // (an estimate on a decided proposal)
@@ -2669,6 +2737,12 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
         // ===== end of iteration: the next proposal (wave 0; draws refilled every 64) =====
         if (wv == 0) {
             if (prof_on && lane == 0) sh.prof[7 + action] += clock64() - sh.t_iter;  // per-action totals
+            if constexpr (REC) {
+                if (it + 1 == rec_next) {  // a sample's phi is exact (phase F made the sums so, unless nothing was evaluated)
+                    phi_r = exact_sums(v.term, v.prefix, v.cprefix, v.cterm, v.rflag, sh, n, lane, false, n, phi_r, 0.0).phi;
+                    if (lane == 0) sh.phi = phi_r;  // read by record_sample after the iteration-end barrier
+                }
+            }
             if ((rbx || xch) && it + 1 == round_end) {  // a tempering round is done: publish phi, take the next temperature
                 {  // (a phase F of this iteration made every sum exact already)
                     phi_r = exact_sums(v.term, v.prefix, v.cprefix, v.cterm, v.rflag, sh, n, lane, false, n, phi_r, 0.0).phi;
@@ -2743,6 +2817,14 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
         __syncthreads();
         STAMP(6);
         SKEW(17);
+        if constexpr (REC) {
+            if (it + 1 == rec_next) {  // this iteration's model into the history (block-uniform)
+                record_sample(d, v.ord, v.ptS, sh, it, iter0, last_action, last_accept, tid, NTH);
+                rec_next += d.rec.every;
+                __syncthreads();  // the copy is done before a later phase G changes the cells, the order or ptS
+                SKEW(19);  // (the profile mode charges the copy to the next iteration's first stamp, phase 0)
+            }
+        }
     }
 
     const long long t_loop_end = prof_on ? clock64() : 0;
@@ -3122,6 +3204,18 @@ __global__ __launch_bounds__(256) void k_draws(const DevChain *__restrict__ dptr
     out[(long long)blockIdx.y * iters + i] = tdchain::draw_iteration(d.seed, d.chain, (uint64_t)(d.st->iter + i));
 }
 
+// A free-running launch outside tempering rounds: the recording instance when the launch records.
+template <bool SMALL, int NTH, bool RLDS>
+static void launch_free(bool rec, int grid, size_t lds, hipStream_t s, const DevChain *dev, int64_t iters,
+                        const ScriptArgs &sa) {
+    if (rec)
+        hipLaunchKernelGGL((k_chain_run<SMALL, false, NTH, RLDS, false, true>), dim3(grid), dim3(NTH), lds, s, dev,
+                           (long long)iters, sa);
+    else
+        hipLaunchKernelGGL((k_chain_run<SMALL, false, NTH, RLDS, false, false>), dim3(grid), dim3(NTH), lds, s, dev,
+                           (long long)iters, sa);
+}
+
 hipError_t chain_run(const DevChain *host, const DevChain *dev, int nchains, int64_t iters, hipStream_t s,
                      const ScriptArgs *script, DrawsBuf db, int num_cus) {
     ScriptArgs sa{};
@@ -3180,6 +3274,9 @@ hipError_t chain_run(const DevChain *host, const DevChain *dev, int nchains, int
         all_auto = all_auto && d.lds_mode == 0;
     }
     const bool scripted = sa.n > 0 || sa.mb != nullptr;
+    bool rec = false;  // a recorded launch (td_chain_run_recorded): the instances that carry the sampling
+    for (int b = 0; b < nchains; ++b) rec = rec || host[b].rec.every > 0;
+    rec = rec && !scripted && sa.rb == nullptr && sa.rx == nullptr;
     // More chains than CUs: one chain per CU would run them in rounds of num_cus workgroups; two
     // 4-wave chains per CU run them all at once (1.35x the 8-wave kernel's rate at 512 config-3
     // chains) -- the tiles-in-LDS kernel when it fits, else the all-in-HBM one
@@ -3198,7 +3295,11 @@ hipError_t chain_run(const DevChain *host, const DevChain *dev, int nchains, int
                               (const void *)k_chain_run<false, false, kChainThreads / 2>,
                               (const void *)k_chain_run<true, false, kChainThreads / 2, false>,
                               (const void *)k_chain_run<true, false, kChainThreads, true, true>,
-                              (const void *)k_chain_run<false, false, kChainThreads, false, true>}) {
+                              (const void *)k_chain_run<false, false, kChainThreads, false, true>,
+                              (const void *)k_chain_run<true, false, kChainThreads, true, false, true>,
+                              (const void *)k_chain_run<false, false, kChainThreads, false, false, true>,
+                              (const void *)k_chain_run<false, false, kChainThreads / 2, false, false, true>,
+                              (const void *)k_chain_run<true, false, kChainThreads / 2, false, false, true>}) {
             hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget);
             if (e != hipSuccess) return e;
         }
@@ -3216,24 +3317,20 @@ hipError_t chain_run(const DevChain *host, const DevChain *dev, int nchains, int
             hipLaunchKernelGGL((k_chain_run<true, true, kChainThreads>), dim3(grid), dim3(kChainThreads), small, s,
                                dev, (long long)iters, sa);
         else
-            hipLaunchKernelGGL((k_chain_run<true, false, kChainThreads>), dim3(grid), dim3(kChainThreads), small, s,
-                               dev, (long long)iters, sa);
+            launch_free<true, kChainThreads, true>(rec, grid, small, s, dev, iters, sa);
     } else if (packed && !scripted && tiles_ok && hyb <= kLdsBudget / 2) {
         // two chains resident per CU (4 waves, <= 80 KB of LDS each): the tiles in LDS, the rays and the
         // order in HBM
-        hipLaunchKernelGGL((k_chain_run<true, false, kChainThreads / 2, false>), dim3(grid), dim3(kChainThreads / 2),
-                           hyb, s, dev, (long long)iters, sa);
+        launch_free<true, kChainThreads / 2, false>(rec, grid, hyb, s, dev, iters, sa);
     } else if (packed && !scripted && half <= kLdsBudget / 2) {
         // rays in HBM, 4 waves and <= 80 KB of LDS per chain: two chains resident per CU
-        hipLaunchKernelGGL((k_chain_run<false, false, kChainThreads / 2>), dim3(grid), dim3(kChainThreads / 2), half,
-                           s, dev, (long long)iters, sa);
+        launch_free<false, kChainThreads / 2, false>(rec, grid, half, s, dev, iters, sa);
     } else {
         if (scripted)
             hipLaunchKernelGGL((k_chain_run<false, true, kChainThreads>), dim3(grid), dim3(kChainThreads), big, s,
                                dev, (long long)iters, sa);
         else
-            hipLaunchKernelGGL((k_chain_run<false, false, kChainThreads>), dim3(grid), dim3(kChainThreads), big, s,
-                               dev, (long long)iters, sa);
+            launch_free<false, kChainThreads, false>(rec, grid, big, s, dev, iters, sa);
     }
     return hipGetLastError();
 }

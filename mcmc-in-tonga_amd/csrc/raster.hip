@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "history.h"
 
 namespace tdstar {
 
@@ -213,15 +214,27 @@ __global__ __launch_bounds__(256) void k_raster_stats(const double *__restrict__
 
 using namespace tdstar;
 
-extern "C" int td_rasterize(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const double *xCell,
-                            const double *yCell, const double *zCell, const double *zeta, const double *qx,
-                            const double *qy, const double *qz, int64_t nq, double *mean_out, double *std_out,
-                            double *values_out) {
+namespace {
+
+// a section's few nodes: every model in one brute-force launch; many nodes: per model,
+// the evaluate path's search (the bucket grid from kGridMinCells cells)
+bool raster_batched(int64_t nmodels, int64_t total, int64_t nq) {
+    return nq * (total / std::max<int64_t>(nmodels, 1)) <= (int64_t)1 << 28 &&
+           (int64_t)kXcds * ((nmodels + kXcds - 1) / kXcds) * ((nq + kRasterNodes - 1) / kRasterNodes) <= INT32_MAX;
+}
+
+// td_rasterize.  segs == nullptr: the cells are the host arrays.  Else (td_history_rasterize, the batched
+// launch only) they are in device memory already: histories' packed samples, segment after segment,
+// copied device to device behind the queries; cell_off is the concatenation's (host) prefix.
+int rasterize_core(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const double *xCell, const double *yCell,
+                   const double *zCell, const double *zeta, const std::vector<td_history *> *segs, const double *qx,
+                   const double *qy, const double *qz, int64_t nq, double *mean_out, double *std_out,
+                   double *values_out) {
     if (!ctx) return set_err(nullptr, TD_ERR_ARG, "td_rasterize: ctx is NULL");
     if (nmodels < 1 || !cell_off || nq < 0 || (nq > 0 && (!qx || !qy || !qz || !mean_out || !std_out)))
         return set_err(ctx, TD_ERR_ARG, "td_rasterize: bad arguments");
     const int64_t total = cell_off[nmodels];
-    if (cell_off[0] != 0 || total < 0 || (total > 0 && (!xCell || !yCell || !zCell || !zeta)))
+    if (cell_off[0] != 0 || total < 0 || (!segs && total > 0 && (!xCell || !yCell || !zCell || !zeta)))
         return set_err(ctx, TD_ERR_ARG, "td_rasterize: bad cell offsets or arrays");
     for (int64_t k = 0; k < nmodels; ++k)
         if (cell_off[k + 1] < cell_off[k]) return set_err(ctx, TD_ERR_ARG, "td_rasterize: offsets not monotone");
@@ -243,7 +256,7 @@ extern "C" int td_rasterize(td_ctx *ctx, int64_t nmodels, const int64_t *cell_of
     const int64_t cs = std::max<int64_t>(total, 1);  // SoA stride of the cells
     // packed into a pinned staging block (reused across calls), then one DMA copy: pageable
     // copies of these sizes run at ~1 GB/s here
-    const size_t nh = 3 * (size_t)nq + 4 * (size_t)cs;
+    const size_t nh = 3 * (size_t)nq + (segs ? 0 : 4 * (size_t)cs);
     if (nh > ctx->h_raster_cap) {
         if (ctx->h_raster) (void)hipHostFree(ctx->h_raster);
         ctx->h_raster = nullptr;
@@ -257,13 +270,23 @@ extern "C" int td_rasterize(td_ctx *ctx, int64_t nmodels, const int64_t *cell_of
     std::memcpy(h + nq, qy, sizeof(double) * (size_t)nq);
     std::memcpy(h + 2 * nq, qz, sizeof(double) * (size_t)nq);
     double *hc = h + 3 * nq;
-    if (total > 0) {
+    if (total > 0 && !segs) {
         std::memcpy(hc, xCell, sizeof(double) * (size_t)total);
         std::memcpy(hc + cs, yCell, sizeof(double) * (size_t)total);
         std::memcpy(hc + 2 * cs, zCell, sizeof(double) * (size_t)total);
         std::memcpy(hc + 3 * cs, zeta, sizeof(double) * (size_t)total);
     }
     TD_HIP(ctx, hipMemcpyAsync(dq, h, sizeof(double) * nh, hipMemcpyHostToDevice, ctx->stream));
+    if (segs) {  // each history's packed samples behind the ones before, component by component
+        int64_t pos = 0;
+        for (const td_history *hh : *segs) {
+            const int64_t cnt = hh->off[(size_t)hh->samples];
+            for (int comp = 0; comp < 4 && cnt > 0; ++comp)
+                TD_HIP(ctx, hipMemcpyAsync(dc + comp * cs + pos, hh->d.cells + comp * hh->d.stride,
+                                           sizeof(double) * (size_t)cnt, hipMemcpyDeviceToDevice, ctx->stream));
+            pos += cnt;
+        }
+    }
     if (nq > ctx->raster_i_cap) {  // nearest-cell indices (not returned)
         if (ctx->raster_i) (void)hipFree(ctx->raster_i);
         ctx->raster_i = nullptr;
@@ -272,10 +295,8 @@ extern "C" int td_rasterize(td_ctx *ctx, int64_t nmodels, const int64_t *cell_of
         ctx->raster_i_cap = nq;
     }
     Timer *tm = ctx->timer.on ? &ctx->timer : nullptr;
-    // a section's few nodes: every model in one brute-force launch; many nodes: per model,
-    // the evaluate path's search (the bucket grid from kGridMinCells cells)
-    const bool batched = nq * (total / std::max<int64_t>(nmodels, 1)) <= (int64_t)1 << 28 &&
-                         (int64_t)kXcds * ((nmodels + kXcds - 1) / kXcds) * ((nq + kRasterNodes - 1) / kRasterNodes) <= INT32_MAX;
+    const bool batched = raster_batched(nmodels, total, nq);
+    if (segs && !batched) return set_err(ctx, TD_ERR_ARG, "td_history_rasterize: internal: per-model path");
     if (batched) {
         if (nmodels + 1 > ctx->raster_off_cap) {
             if (ctx->raster_off) (void)hipFree(ctx->raster_off);
@@ -329,4 +350,50 @@ extern "C" int td_rasterize(td_ctx *ctx, int64_t nmodels, const int64_t *cell_of
                                    ctx->stream));
     TD_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return TD_OK;
+}
+
+}  // namespace
+
+extern "C" int td_rasterize(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const double *xCell,
+                            const double *yCell, const double *zCell, const double *zeta, const double *qx,
+                            const double *qy, const double *qz, int64_t nq, double *mean_out, double *std_out,
+                            double *values_out) {
+    return rasterize_core(ctx, nmodels, cell_off, xCell, yCell, zCell, zeta, nullptr, qx, qy, qz, nq, mean_out,
+                          std_out, values_out);
+}
+
+extern "C" int td_history_rasterize(td_ctx *ctx, td_history *const *hs, int64_t nh, const double *qx,
+                                    const double *qy, const double *qz, int64_t nq, double *mean_out,
+                                    double *std_out, double *values_out) {
+    if (!ctx) return set_err(nullptr, TD_ERR_ARG, "td_history_rasterize: ctx is NULL");
+    if (!hs || nh < 1) return set_err(ctx, TD_ERR_ARG, "td_history_rasterize: no history");
+    std::vector<td_history *> segs;
+    std::vector<int64_t> off(1, 0);  // the concatenation's prefix, from the histories' host mirrors
+    for (int64_t i = 0; i < nh; ++i) {
+        td_history *h = hs[i];
+        if (!h || h->ctx != ctx)
+            return set_err(ctx, TD_ERR_ARG, "td_history_rasterize: every history must be non-NULL and of this context");
+        const int64_t base = off.back();
+        for (int64_t k = 1; k <= h->samples; ++k) off.push_back(base + h->off[(size_t)k]);
+        if (h->samples > 0) segs.push_back(h);
+    }
+    const int64_t nmodels = (int64_t)off.size() - 1;
+    if (nmodels < 1) return set_err(ctx, TD_ERR_ARG, "td_history_rasterize: the histories hold no sample");
+    if (raster_batched(nmodels, off.back(), nq))
+        return rasterize_core(ctx, nmodels, off.data(), nullptr, nullptr, nullptr, nullptr, &segs, qx, qy, qz, nq,
+                              mean_out, std_out, values_out);
+    // the per-model search computes each model's bounding box on the host: fetch the cells
+    const size_t total = (size_t)std::max<int64_t>(off.back(), 1);
+    std::vector<double> c(4 * total);
+    size_t pos = 0;
+    for (td_history *h : segs) {
+        const int64_t cnt = h->off[(size_t)h->samples];
+        int rc = td_history_read(h, 0, h->samples, nullptr, c.data() + pos, c.data() + total + pos,
+                                 c.data() + 2 * total + pos, c.data() + 3 * total + pos, cnt, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr);
+        if (rc) return rc;
+        pos += (size_t)cnt;
+    }
+    return rasterize_core(ctx, nmodels, off.data(), c.data(), c.data() + total, c.data() + 2 * total,
+                          c.data() + 3 * total, nullptr, qx, qy, qz, nq, mean_out, std_out, values_out);
 }

@@ -143,6 +143,20 @@ class TdContext:
                                  ptr(qz), nq, ptr(mean), ptr(std), ptr(vals) if want_values else None), self.h)
         return mean, std, vals
 
+    def rasterize_history(self, histories, qx, qy, qz, want_values=False):
+        """td_history_rasterize: ``rasterize`` on the samples of the histories (chain.History), history
+        by history in sample order, without the models visiting the host."""
+        histories = list(histories)
+        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
+        nm = sum(len(h) for h in histories)
+        qx, qy, qz = (f64(np.ravel(a)) for a in (qx, qy, qz))
+        nq = len(qx)
+        mean, std = np.empty(nq), np.empty(nq)
+        vals = np.empty((nm, nq)) if want_values else None
+        check(lib().td_history_rasterize(self.h, hs, len(histories), ptr(qx), ptr(qy), ptr(qz), nq, ptr(mean),
+                                         ptr(std), ptr(vals) if want_values else None), self.h)
+        return mean, std, vals
+
     def interpolate(self, cells, X, Y, Z, want_nearest=False):
         """-> (zeta[npoints], nearest[npoints] or None)"""
         xc, yc, zc, ze = (f64(c) for c in cells)

@@ -24,7 +24,8 @@ def _flatten(model_hist):
 
 
 def section(ctx, models, xs, ys, zs, axis):
-    """One cross-section: axis "xz" (ys a scalar) or "xy" (zs a scalar).
+    """One cross-section: axis "xz" (ys a scalar) or "xy" (zs a scalar); ``models``: Model objects, or
+    device histories (chain.History).
     Returns (mean, std) as len(first) x len(second) matrices."""
     if axis == "xz":
         a, b = np.asarray(xs, dtype=np.float64), np.asarray(zs, dtype=np.float64)
@@ -36,15 +37,22 @@ def section(ctx, models, xs, ys, zs, axis):
         qz = np.full(qx.shape, float(zs))
     else:
         raise ValueError(axis)
-    mean, std, _ = ctx.rasterize([m.cells() for m in models], qx, qy, qz)
+    if models and all(hasattr(m, "read_arrays") for m in models):  # chain.History: rasterised where they lie
+        mean, std, _ = ctx.rasterize_history(models, qx, qy, qz)
+    else:
+        mean, std, _ = ctx.rasterize([m.cells() for m in models], qx, qy, qz)
     shape = (len(b), len(a))  # column-major nx x n2 matrix, xs fastest
     return mean.reshape(shape).T.copy(), std.reshape(shape).T.copy()
 
 
 def plot_model_hist(model_hist, dataStruct, TD_parameters, cmax=None):  # noqa: N802 -- reference name
     """MCsub.jl:753-825 without the plots: {("xz", y) | ("xy", z): {"mean",
-    "std", "masked"}} with masked = mean where std <= 5, NaN elsewhere (:776-781)."""
+    "std", "masked"}} with masked = mean where std <= 5, NaN elsewhere (:776-781).
+    ``model_hist`` may also be a ``History`` or a list of them (one per chain): their samples, history
+    by history, are the models, and stay on the device (td_history_rasterize)."""
     ctx = context_for(dataStruct)
+    if hasattr(model_hist, "read_arrays"):
+        model_hist = [model_hist]
     models = _flatten(model_hist)
     xv, yv, zv = (np.asarray(v, dtype=np.float64) for v in (dataStruct.xVec, dataStruct.yVec, dataStruct.zVec))
     maps = {}
