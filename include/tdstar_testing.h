@@ -40,8 +40,16 @@ int tdt_propose(const td_chain_params *prm, uint64_t iter, int64_t ncells, const
 int tdt_chain_profile(td_chain *ch, int enable, int64_t out[80]);
 /* LDS plan of a device chain: [0] bytes of the LDS layout (tiles, rays and
  * order mirrored), [1] bytes of the HBM layout, [2] 1 if the HBM layout holds
- * its super-tiles in LDS, [3] 1 if runs take the LDS layout. */
+ * its super-tiles in LDS, [3] 1 if a free-running launch of this chain alone
+ * takes the LDS layout (it fits and the chain's lds_mode is 0). */
 int tdt_chain_lds(td_chain *ch, int64_t out[4]);
+/* The k_chain_run instance and dynamic LDS size a launch takes (csrc/chain_variant.h; host only, no
+ * context).  in: [0..3] the chains' largest LDS plans small, big, half, hyb; [4..7] force_hbm, packed,
+ * tiles_ok, all_auto (over the chains' lds_mode); [8] scripted, [9] some chain records, [10] exchange
+ * rounds, [11] resident tempering rounds; [12] nchains, [13] num_cus, [14] the LDS budget.
+ * out: [0..5] SMALL, SCRIPT, NTH, RLDS, ROUNDS, REC; [6] LDS bytes; [7] the instance's index in the
+ * launcher's table of 12, -1 if it has none (the launch would fail). */
+int tdt_chain_variant(const int64_t in[15], int64_t out[8]);
 /* Cycles of nq back-to-back nearest-cell queries through the chain's bucket grid by one wave
  * (pts: nq x {x, y, z}); mode 0: the whole query, 1: its loads only, 2: its arithmetic only.
  * out[0] = cycles, out[1] = unproven queries (full scans). */

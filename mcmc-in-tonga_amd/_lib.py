@@ -104,6 +104,7 @@ SIGNATURES = {
     "tdt_propose": (ctypes.c_int, [ctypes.POINTER(TdChainParams), _u64, _i64, _pd, _pd, _pd, _pd, _d, _pd]),
     "tdt_chain_profile": (ctypes.c_int, [_vp, ctypes.c_int, _pi64]),
     "tdt_chain_lds": (ctypes.c_int, [_vp, _pi64]),
+    "tdt_chain_variant": (ctypes.c_int, [_pi64, _pi64]),
     "tdt_chain_query_lat": (ctypes.c_int, [_vp, _pd, ctypes.c_int, ctypes.c_int, _pi64]),
     "tdt_chain_query_answers": (ctypes.c_int, [_vp, _pd, ctypes.c_int, ctypes.c_int, _pd, _pd, _pi32]),
     "tdt_tile_filter": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _pd,

@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "chain_logic.h"
+#include "chain_variant.h"
 #include "internal.h"
 #include "../../include/tdstar.h"
 
@@ -280,12 +281,17 @@ struct DrawsBuf {
 // Build the cache from scratch for the cells currently in slots 0..ncells-1
 // (order = rank = identity): nearest search, ray sums, chi^2 prefix, tile maxima.
 hipError_t chain_full_state(DevChain &d, int ncells, NNWork &work, int num_cus, hipStream_t s);
+// Its last-but-one step alone, k_chi2_prefix (chain_state.hip): the sequential chi^2 prefix sums and phi
+hipError_t launch_chi2_prefix(const double *ptS, const double *tS, const double *sig, int n, double *prefix,
+                              ChainScalars *st, hipStream_t s);
 // Run `iters` iterations of `nchains` chains, one persistent workgroup each
 // (workgroup b runs chain b).  `host` = the descriptors, `dev` = their device
 // copy, contiguous (the kernel reads its fields from global memory).
 hipError_t chain_run(const DevChain *host, const DevChain *dev, int nchains, int64_t iters, hipStream_t s,
                      const ScriptArgs *script = nullptr, DrawsBuf db = DrawsBuf{nullptr, nullptr},
                      int num_cus = 0);  // > 0: a batch of more chains than CUs packs two per CU
+// The k_chain_run instance chain_run launches for `v`: its index in chain_run's table, -1 if none (host only)
+int chain_variant_index(const ChainVariant &v);
 // Testing: the chain's chi^2 code on a caller-given ptS (n <= 4096) --
 // path 2: k_chi2_prefix (the starting state's sequential prefix sums, what
 // chain_full_state runs), 3: the proposal-time sum (the terms of MCsub.jl:171,

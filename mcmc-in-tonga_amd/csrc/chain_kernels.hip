@@ -1,6 +1,7 @@
 // chain_kernels.hip -- the device-resident rj-MCMC chain (TD_ENGINE_DEVICE).
 //
-// One persistent 1024-thread workgroup runs `iters` iterations of
+// One persistent workgroup per chain -- 512 threads, or 256 where two chains share a CU -- runs `iters`
+// iterations of
 // TD_inversion_function.jl:70-274 without returning to the host: draw the
 // proposal (chain_logic.h, shared with the host engine), evaluate it
 // incrementally against the cached per-point nearest cells (chain_dev.h),
@@ -24,6 +25,15 @@
 //   * candidate flags are cleared, and the bucket grid updated, at the start of
 //     the NEXT iteration, off the critical path;
 //   * the sequential chi^2 tail runs on one lane from LDS, 8 terms per trip.
+//
+// This unit: the proposal helpers, the rare exact sums, the recorded sample, k_chain_run with its 12
+// instances, the one-point query (k_chain_query), the pre-drawn draws (k_draws) and the host launchers
+// chain_run and chain_query.  What the kernel is built
+// from sits in headers by concern: chain_shared.h (the Shared block, the LDS plan, Views),
+// chain_search.h (nearest cell through the bucket grid), chain_tiles.h (the tile filters),
+// chain_resident.h (the mailbox server and the tempering-round protocols), chain_diag.h (STAMP, SKEW,
+// SPIN_WAIT, BPROBE); chain_variant.h chooses the instance.  The full-state kernels are in
+// chain_state.hip, the testing kernels in chain_test_kernels.hip.
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -34,6 +44,12 @@
 #include <cstdlib>
 
 #include "chain_dev.h"
+#include "chain_diag.h"
+#include "chain_resident.h"
+#include "chain_search.h"
+#include "chain_shared.h"
+#include "chain_tiles.h"
+#include "chain_variant.h"
 #include "exact_sum.h"
 #include "internal.h"
 #include "ray_sum.h"
@@ -43,59 +59,6 @@ namespace tdstar {
 
 namespace {
 
-using tdchain::Proposal;
-
-constexpr int kWaves = kChainThreads / 64;
-static_assert(kTilePts == 16, "a tile is one 16-lane DPP row (row_max_u64)");
-constexpr int kOrphanLds = 96;  // orphan records kept in LDS (more: read back from HBM)
-constexpr int kPre = 64 / kTilePts;  // LDS layout: hit tiles per wave whose points phase B preloads
-static_assert(kPre == 4, "the preload slots are four registers");
-constexpr int kCtmLds = 256;    // tiles in LDS, rays in HBM: hit tiles' candidate maxima kept in LDS
-constexpr int kListLds = 1024;
-// LDS layout, phase D: from this many orphans on, one search for all of them (the bucket region
-// around them staged once in LDS, a thread per orphan) instead of one wave's grid search each
-constexpr int kBatchOrphans = 64;
-constexpr int kBatchCand = 192;     // cell entries staged (phase E's idle ray scratch: 28 B each)
-constexpr int kBatchBuckets = 512;  // buckets in the region at most  // rays in HBM: hit tiles / changed rays / hit super-tiles kept in LDS
-// Phase C leaves lanes idle (16 per hit tile, ~8 tiles): wave 7 lane 0 forms the decision's
-// phi_n-free parts; wave 6 lane 0 (LDS layout) begins the next proposal's guess -- its global loads
-// fly across the phase barriers until phase F finishes it there
-// The LDS layout could sum chi^2 with the event walk too; its tails are ~60 terms and the
-// one-wave binade scan with the early-rejection bound is faster there (measured: the walk
-// costs ~1.2k more cycles per proposal at 381 rays x 5000 cells)
-constexpr bool kSmallWalk = false;
-
-// A changed point's candidate (what mark() stores in the overlay), kept in LDS for the first kChgLds of
-// a proposal: phase G commits them from here with stores only -- no dependent round trips to the
-// changed list and the overlay in HBM
-struct ChgRec {
-    int q, s;
-    double d, z;
-};
-constexpr int kChgLds = 64;
-
-// A point whose nearest cell is removed or moved: re-searched in phase D.
-struct OrphanRec {
-    double x, y, z;
-    int q, ray;
-};
-
-__device__ __forceinline__ double dist2(double cx, double cy, double cz, double x, double y, double z) {
-    // (mx-x)^2 + (my-y)^2 + (mz-z)^2, MCsub.jl:254 -- same ops as k_nn_partial
-    const double dx = cx - x, dy = cy - y, dz = cz - z;
-    double d = dx * dx;
-    d = d + dy * dy;
-    d = d + dz * dz;
-    return d;
-}
-
-// (distance, Julia position) lexicographic order; a cell must also beat the
-// 1e9 sentinel strictly (MCsub.jl:250,255).
-template <class R>
-__device__ __forceinline__ bool better(double d, R r, double bd, R br) {
-    return d < bd || (d == bd && d < kSentinel && r < br);
-}
-
 struct OverlayZeta {
     const unsigned char *flag;
     const double *cand, *cur;
@@ -103,13 +66,6 @@ struct OverlayZeta {
         const double a = cand[k], b = cur[k];  // both loads issued at once, then select
         return flag[k] ? a : b;
     }
-};
-
-// A proposal with what it needs from the model (tid 0 builds it).
-struct PState {
-    Proposal p;
-    double kx, ky, kz, zeta_killed;  // site and value of the selected cell (not birth)
-    int slot_k, new_slot, eval;
 };
 
 // TD_inversion_function.jl:72-80,127-128,184-188,221-232: the proposal of one
@@ -205,120 +161,6 @@ __device__ __forceinline__ void script_proposal(PState &o, const ScriptStep &st,
     o.eval = 1;
 }
 
-// The bucket grid's geometry and arrays, copied into LDS when a launch starts: a query reads them in
-// one round of LDS loads rather than one scalar load (and wait) per descriptor field, and bounds the
-// block without branches (wave_grid_search)
-struct GridGeo {
-    double x0, y0, z0, ix, iy, iz, hx, hy, hz, ex, ey, ez;
-    double lo[3], hi[3];
-    // a bound every query may use first: each face of a query's 3x3x3 block is at least h - e (the
-    // cells' allowance) - e (the query's own bucket rounding, within the same allowance) away on its
-    // axis, so every cell outside the block is at least lb0 away (+inf when no axis can have a face)
-    double lb0;
-    const int *count;
-    const CellEntry *buckets;
-    const int *bslot;
-    int gx, gy, gz, sealed;
-};
-__device__ __forceinline__ void geo_fill(GridGeo &g, const DevChain &d) {
-    const CellGrid &G = d.grid;
-    g.x0 = G.x0; g.y0 = G.y0; g.z0 = G.z0;
-    g.ix = G.ix; g.iy = G.iy; g.iz = G.iz;
-    g.hx = G.hx; g.hy = G.hy; g.hz = G.hz;
-    g.ex = G.ex; g.ey = G.ey; g.ez = G.ez;
-    for (int a = 0; a < 3; ++a) {
-        g.lo[a] = G.lo[a];
-        g.hi[a] = G.hi[a];
-    }
-    g.count = d.bucket_count;
-    g.buckets = d.buckets;
-    g.bslot = d.bslot;
-    g.gx = G.gx; g.gy = G.gy; g.gz = G.gz;
-    g.sealed = G.sealed;
-    const double h3[3] = {G.hx, G.hy, G.hz}, e3[3] = {G.ex, G.ey, G.ez};
-    const int g3[3] = {G.gx, G.gy, G.gz};
-    double lb0 = __builtin_huge_val();
-    for (int a = 0; a < 3; ++a) {
-        if (g3[a] < 3) continue;  // the block spans the axis: no face on it
-        const double gap = (h3[a] - 2.0 * e3[a]) * (1.0 - 0x1p-30);
-        const double f = gap > 0.0 ? gap * gap : 0.0;
-        lb0 = f < lb0 ? f : lb0;
-    }
-    g.lb0 = grid_lb_close(lb0);
-}
-
-struct Shared {
-    GridGeo geo;       // the bucket grid (geo_fill at a launch's start)
-    PState ps[2];      // this iteration's proposal (ps[cur]) and the next one guessed in phase F
-    int cur, spec_ok;
-    int defer;  // phase F: accepted on bounds (LDS layout): the new chi^2 partial sums are not formed
-    double phi_n;
-    // decisions on bounds (phase F; wave 0): prefix[] exact below ex_upto, phi_r an
-    // estimate in [phi_lo, phi_hi] (held here, not in registers: the kernel is at its VGPR limit)
-    int ex_upto;
-    double phi_lo, phi_hi, b_lo, b_hi;
-    // The proposal's counters (atomic adds in phases B-E; wave 0 clears them at the iteration's end for the
-    // next one).  No wave reads them after phase F's barrier: phase G reads the snapshot gs instead.
-    int n_tiles, n_changed, n_orphans, n_rays, k0;
-    // What phase G needs of the proposal, taken by tid 0 in phase F before its barrier (the counters are
-    // final by then: n_tiles after B, the others after D) and read after it; written again only in the next
-    // iteration's phase F, after the iteration-end barrier -- so nothing writes it while a wave may read it,
-    // and the counters above can be cleared at the iteration's end whatever the waves' skew.  accept: the
-    // decision (phase F), or a server's next command (phase G, wave 0, then a block barrier).
-    struct GSnap {
-        int nc, nr, nt, k0, accept;
-    } gs;
-    int ob_lo[3], ob_hi[3], ob_ncand, ob_nfb;  // phase D's orphan-batch search (LDS layout)
-    int n_super[2];  // rays in HBM: super-tiles hit, by iteration parity (the next iteration refreshes their maxima)
-    int pts_seen, ray_pts;
-    int e_done;  // LDS layout: waves done with their phase-E rays (waves 1..; wave 0 waits for them)
-    int b_done;  // LDS layout: waves done with their phase-B tile pass (phase B without its barrier)
-    // bucket-grid update of an accepted proposal (applied by the last wave in phase G)
-    int g_op, g_slot;           // bit 1: remove at old site, bit 2: insert at new site, bit 4: new value in place
-    // what the update needs from the grid, read during phase F (G only writes)
-    int gp_bo, gp_co, gp_pos, gp_bn, gp_cn;
-    CellEntry gp_last;
-    int gp_last_slot;
-    double g_nzeta;
-    double g_ox, g_oy, g_oz, g_nx, g_ny, g_nz;
-    // chain scalars, resident for the whole launch
-    long long iter, evaluations, bytes;
-    long long proposed[5], accepted[5];
-    double phi;
-    int ncells, nslots, nfree;
-    long long next_stamp;  // the next birth's stamp (tid 0)
-    double lnN[3];     // logN[ncells - 1 .. ncells + 1]
-    double lnN_far[2];  // logN[ncells - 2], logN[ncells + 2]: read during phase F for a birth/death commit
-    double q_zeta;         // result of the birth/death Interpolation query
-    int grid_fallbacks32;  // grid searches that needed the full scan
-    int grid_ovf;          // LDS copy of *d.grid_overflow
-    // scripted / server steps: the current step, a server command's steps
-    ScriptStep step_cur;
-    ScriptStep srv_step[kMaxScript];
-    int srv_n, srv_k, srv_quit;
-    // resident tempering rounds: the temperature of the current round (for reject_bound) and its last seq
-    double rT, rinv2t;
-    long long rseq;
-    int rK, rskip;
-    long long srv_seq, srv_busy_c, srv_busy_w;
-    long long mbox[40];  // server mode: the last command read from the mailbox
-    OrphanRec orph[kOrphanLds];
-    ChgRec chg[kChgLds];
-    tdchain::AlphaParts ap;  // the decision's phi-free part (phase C, last wave), for phase F
-    DeltaSegs dseg;  // rays in HBM: phase F's new chi^2 partial sums as segments over the old ones
-    long long prof[kProfSlots], t_last, t_iter;  // diagnostic phase stamps
-    // rays in HBM: the committed terms' sum kept in any order, |tsum - (the exact real sum)| <=
-    // terr; a proposal adds dsum = its terms' changes (any order), dabs = their magnitudes (phase E)
-    double tsum, terr, dsum, dabs, b_T, b_E;
-    double wpart[kChainThreads / 64];  // each wave's part of a block-wide any-order sum of the terms
-    // a death, rays in LDS, free-running: phase G's deleteat! shift (shift_range) by waves 1.. -- each
-    // wave's last source read in phase F (shift_edge), the waves done counted in shift_done, which wave 0
-    // waits for before it reads the order for the next proposal
-    int shift_done;
-    int shift_edge[kChainThreads / 64];
-    int dbg_site[kChainThreads / 64];  // the skew build's trail: each wave's last skew site (SKEW)
-};
-
 // deleteat! at Julia position `index` (rays in LDS, free-running): positions index+1 .. ncells-1 move down
 // one, wave w (1 .. nw) taking the source positions [a, b).  Each wave reads its sources and writes
 // them one lower in passes of 64 (a pass reads before it writes); the one source another wave writes
@@ -328,901 +170,6 @@ __device__ __forceinline__ void shift_range(int index, int ncells, int w, int nw
     a = first + (w - 1) * C;
     b = min(a + C, ncells);
 }
-
-// Diagnostic phase stamp (lane 0 of wave 0, right after a barrier): cycles
-// since the previous stamp are charged to phase k.  Off unless d.profile.
-#define STAMP(k)                                   \
-    do {                                           \
-        if (prof_on && tid == 0) {                 \
-            const long long t_ = clock64();        \
-            sh.prof[k] += t_ - sh.t_last;          \
-            sh.prof[16 + 10 * (action - 1) +       \
-                    ((k) <= 5 ? (k) : (k) == 12 ? 6 : (k) == 13 ? 7 : 8)] += t_ - sh.t_last; \
-            sh.t_last = t_;                        \
-        }                                          \
-    } while (0)
-
-// Wave-skew testing build (-DTD_CHAIN_SKEW, tools/build_skew.sh): after every block barrier and every
-// barrier-free phase end of the chain loop, one wave -- rotating with the iteration and the site --
-// sleeps 8k-16k cycles (a whole phase or more), so any shared word read without a synchronisation
-// that orders it shows up as a wrong answer in the chain parity tests.  Off in the product build.
-#ifdef TD_CHAIN_SKEW
-#define SKEW(site)                                                                      \
-    do {                                                                                \
-        if (lane == 0) sh.dbg_site[wv] = (int)((it << 8) | (site));                     \
-        if (wv == (int)(((unsigned long long)it * 5ull + (site)) % (unsigned)kWv)) {    \
-            __builtin_amdgcn_s_sleep(127);                                              \
-            if (((it + (site)) & 1) != 0) __builtin_amdgcn_s_sleep(127);                \
-        }                                                                               \
-    } while (0)
-#else
-#define SKEW(site) \
-    do {           \
-    } while (0)
-#endif
-// The chain's spin waits (a wave waiting for other waves' counts in LDS).  In the skew build each gives up
-// after ~0.5 s, adds `site` to the diagnostic slot prof[79] (tdt_chain_profile) and goes on, so a wait that
-// can never end shows up as a wrong answer and a nonzero slot instead of a hung launch.
-#ifdef TD_CHAIN_SKEW
-// (the first time one gives up, prof[56 + w] holds wave w's last skew site, as it << 8 | site, and
-// prof[64] the iteration << 8 | the giving-up wave)
-#define SPIN_WAIT(cond, site)                                                                        \
-    do {                                                                                             \
-        long long n_ = 0;                                                                            \
-        while (cond) {                                                                               \
-            __builtin_amdgcn_s_sleep(1);                                                             \
-            if (++n_ > (1ll << 23)) {                                                                \
-                if (lane == 0) {                                                                     \
-                    if (atomicAdd((unsigned long long *)&sh.prof[79], (unsigned long long)(site)) == 0ull) { \
-                        for (int w_ = 0; w_ < kWv; ++w_) sh.prof[56 + w_] = sh.dbg_site[w_];       \
-                        sh.prof[64] = (it << 8) | wv;                                                \
-                    }                                                                                \
-                }                                                                                    \
-                break;                                                                               \
-            }                                                                                        \
-        }                                                                                            \
-    } while (0)
-#else
-#define SPIN_WAIT(cond, site)                      \
-    do {                                           \
-        while (cond) __builtin_amdgcn_s_sleep(1);  \
-    } while (0)
-#endif
-
-// Phase-B probe build (-DTD_B_PROBE, diagnostics only): tid 0's cycles from the phase's start (STAMP(0)) to
-// points inside phase B, summed into prof[72 + k] (those slots' preamble use is off in that build).
-#ifdef TD_B_PROBE
-#define BPROBE(k)                                                       \
-    do {                                                                \
-        if (prof_on && tid == 0) sh.prof[72 + (k)] += clock64() - sh.t_last; \
-    } while (0)
-#else
-#define BPROBE(k) \
-    do {          \
-    } while (0)
-#endif
-
-// LDS carve-up (host and device agree on it through this function).
-struct LdsPlan {
-    size_t scratch, draws, smask, cmask, slo, shi, smax, shit, hrec, rhitl, tlo, thi, tmaxd, tstart, thit, ctm, tray, rayoff, ptS, prefix, cptS, cprefix, term, cterm,
-        tS, sig, rflag, rhit, ord, total;
-    bool super_lds;  // rays in HBM: super-tile boxes, maxima and hit lists in LDS
-    bool lists_lds;  // rays in HBM: the first kListLds hit tiles (as records) and changed rays in LDS
-};
-
-constexpr size_t kLdsBudget = 160 * 1024;
-constexpr size_t kDrawsBudget = (size_t)256 << 20;  // precomputed draws of one launch, at most (chain_run)
-
-__host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-// small: the tiles in LDS (and, rays_lds, the per-ray arrays and the order too -- else those stay in
-// HBM, and the first kCtmLds hit tiles' candidate maxima are in LDS: the 4-wave two-chains-per-CU
-// kernel's "tiles" layout)
-__host__ __device__ inline LdsPlan lds_plan(int ntiles, int n, int cap, bool small, int waves = kWaves,
-                                            bool rays_lds = true) {
-    LdsPlan L{};
-    size_t o = align16(sizeof(Shared));
-    L.scratch = o; o += align16(sizeof(double) * waves * (small ? 96 : 192));  // (HBM layout: two rays a wave)
-    L.draws = o; o += align16(sizeof(tdchain::Draws) * 64);                     // 64 iterations ahead
-    if (!small || kSmallWalk) {  // the chi^2 walk's event words (exact_sum.h): static ones, kept; changed rays
-        L.smask = o; o += align16(sizeof(unsigned long long) * delta_words(n));
-        L.cmask = o; o += align16(sizeof(unsigned long long) * delta_words(n));
-    }
-    if (small) {
-        L.tlo = o; o += align16(sizeof(float) * 3 * ntiles);
-        L.thi = o; o += align16(sizeof(float) * 3 * ntiles);
-        L.tmaxd = o; o += align16(sizeof(double) * ntiles);
-        L.tstart = o; o += align16(sizeof(int) * (ntiles + 1));
-        L.thit = o; o += align16(sizeof(int) * (ntiles + 1));
-        L.ctm = o; o += align16(sizeof(double) * (rays_lds ? ntiles + 1 : kCtmLds));
-        L.tray = o; o += align16(sizeof(int) * ntiles);
-        if (rays_lds) {
-            L.rayoff = o; o += align16(sizeof(int) * (n + 1));
-            L.ptS = o; o += align16(sizeof(double) * n);
-            L.prefix = o; o += align16(sizeof(double) * n);
-            L.cptS = o; o += align16(sizeof(double) * n);
-            L.cprefix = o; o += align16(sizeof(double) * n);
-            L.term = o; o += align16(sizeof(double) * n);
-            L.cterm = o; o += align16(sizeof(double) * n);
-            L.tS = o; o += align16(sizeof(double) * n);
-            L.sig = o; o += align16(sizeof(double) * n);
-            L.rflag = o; o += align16(sizeof(int) * n);
-            L.rhit = o; o += align16(sizeof(int) * n);
-            L.ord = o; o += align16(sizeof(int) * cap);
-        }
-    } else {
-        // the first hit tiles as {tile, start << 5 | count, ray} records, the first changed rays
-        size_t q = o;
-        L.hrec = q; q += align16(sizeof(int4) * kListLds);
-        L.rhitl = q; q += align16(sizeof(int) * kListLds);
-        L.lists_lds = q <= kLdsBudget;
-        if (L.lists_lds) o = q;
-        // super-tiles (16 tiles each): boxes, maxima (FP32, rounded up), two hit lists
-        const int ns = (ntiles + kTilePts - 1) / kTilePts;
-        q = o;
-        L.slo = q; q += align16(sizeof(float) * 3 * ns);
-        L.shi = q; q += align16(sizeof(float) * 3 * ns);
-        L.smax = q; q += align16(sizeof(float) * ns);
-        L.shit = q; q += align16(sizeof(int) * 2 * kListLds);
-        L.super_lds = q <= kLdsBudget;
-        if (L.super_lds) o = q;
-    }
-    L.total = o;
-    return L;
-}
-
-// Views of the arrays a launch works on: LDS copies in SMALL mode, else HBM.
-struct Views {
-    const float *tlo, *thi;
-    double *tmaxd, *ptS, *prefix, *cptS, *cprefix, *term, *cterm;
-    const double *tS, *sig;
-    const int *tstart, *ray_off, *tray;
-    int *thit, *rflag, *rhit, *ord;
-    // rays in HBM: the first kListLds changed rays in LDS (rhit), the rest in rhit_g;
-    // the first kListLds hit tiles also as LDS records
-    int *rhit_g;
-    int rhit_cap;
-    int4 *hrec;
-    int hrec_cap;
-    // hit tile i's maximum if the proposal is accepted: the first ctm_cap in LDS (ctm), the rest in ctm_g
-    double *ctm, *ctm_g;
-    int ctm_cap;
-    __device__ __forceinline__ double ctm_at(int i) const { return i < ctm_cap ? ctm[i] : ctm_g[i]; }
-    __device__ __forceinline__ void ctm_put(int i, double x) const {
-        if (i < ctm_cap) ctm[i] = x;
-        else ctm_g[i] = x;
-    }
-    __device__ __forceinline__ int ray_at(int i) const { return i < rhit_cap ? rhit[i] : rhit_g[i]; }
-    __device__ __forceinline__ void ray_put(int i, int r) const {
-        if (i < rhit_cap) rhit[i] = r;
-        else rhit_g[i] = r;
-    }
-    // hit tile i: {tile, start << 5 | count, ray}
-    __device__ __forceinline__ int4 tile_rec(int i) const {
-        if (i < hrec_cap) return hrec[i];
-        const int t = thit[i] & 0x7fffffff;  // LDS layout: the high bit marks a tile preloaded in phase B
-        return int4{t, tstart[t], tray[t], 0};
-    }
-};
-
-// Result of one nearest-cell query, the same in every lane of the wave.
-struct Nearest {
-    double d, z;  // squared distance (1e9 sentinel if none) and the cell's value (0.0 if none)
-    int s;        // slot (-1 if none)
-    bool proven;
-};
-
-// Exact nearest live cell by scanning every slot, ONE wave: lexicographic
-// (distance, Julia position), which is what v_nearest's first-index rule
-// gives (MCsub.jl:250-258) -- positions compared through the slots' stamps,
-// which are in Julia order (chain_dev.h).  Fallback of the grid search (rare:
-// out of line).
-__device__ __attribute__((noinline)) Nearest wave_full_scan(const long long *__restrict__ stamp,
-                                                           const double *__restrict__ cx,
-                                                           const double *__restrict__ cy,
-                                                           const double *__restrict__ cz,
-                                                           const double *__restrict__ czeta, int cap, int nslots,
-                                                           int lane, double x, double y, double z, int skip,
-                                                           int moved, double mx, double my, double mz) {
-    double bd = kSentinel;
-    long long br = LLONG_MAX;
-    int bs = -1;
-    constexpr int kScanUnroll = 8;  // all loads of a round issued before any use
-    for (int s0 = lane; s0 < nslots; s0 += kScanUnroll * 64) {
-        long long r[kScanUnroll];
-        double px[kScanUnroll], py[kScanUnroll], pz[kScanUnroll];
-#pragma unroll
-        for (int u = 0; u < kScanUnroll; ++u) {
-            // unconditional loads from a clamped slot, masked afterwards
-            const int s = min(s0 + u * 64, cap - 1);
-            r[u] = stamp[s];
-            px[u] = cx[s];
-            py[u] = cy[s];
-            pz[u] = cz[s];
-        }
-#pragma unroll
-        for (int u = 0; u < kScanUnroll; ++u) {
-            const int s = s0 + u * 64;
-            if (s >= nslots || r[u] < 0 || s == skip) continue;  // free slot / killed cell
-            if (s == moved) {
-                px[u] = mx;
-                py[u] = my;
-                pz[u] = mz;
-            }
-            const double dd = dist2(px[u], py[u], pz[u], x, y, z);
-            if (better(dd, r[u], bd, br)) {
-                bd = dd;
-                br = r[u];
-                bs = s;
-            }
-        }
-    }
-    // lexicographic min: the distance first, then the position among equals
-    const unsigned long long kd = wave_min_u64((unsigned long long)__double_as_longlong(bd));
-    const bool at_min = (unsigned long long)__double_as_longlong(bd) == kd;
-    const unsigned long long kr = wave_min_u64(at_min ? (unsigned long long)br : ~0ull);
-    Nearest res;
-    res.d = __longlong_as_double((long long)kd);
-    res.proven = true;
-    if (res.d < kSentinel && kr != ~0ull) {  // (stamps are unique: one lane holds the winner)
-        const unsigned long long who = __ballot(at_min && (unsigned long long)br == kr);
-        res.s = __builtin_amdgcn_readlane(bs, __builtin_ctzll(who));
-        res.z = czeta[res.s];
-    } else {
-        res.s = -1;
-        res.z = 0.0;
-    }
-    return res;
-}
-
-// Nearest live cell through the bucket grid, ONE wave, no block barrier.
-// Lanes 0..53 cover the 3x3x3 buckets around the query, 8 entries per bucket
-// (entries hold the cell coordinates inline: ONE round of loads).  The answer
-// is proven when its distance is strictly below the squared distance to the
-// outer faces of the block (every cell outside lies beyond a face), no other
-// entry ties it and no bucket holds more than 8 entries.  `skip` = the killed
-// slot; slot `moved` is taken at (mx,my,mz) instead of its stored site.
-__device__ __forceinline__ Nearest wave_grid_search(const DevChain &d, bool ovf, int lane, double x, double y,
-                                                    double z, int skip, int moved, double mx, double my, double mz,
-                                                    double mzeta) {
-    const CellGrid &G = d.grid;
-    const int bi = grid_axis(x, G.x0, G.ix, G.gx), bj = grid_axis(y, G.y0, G.iy, G.gy),
-              bk = grid_axis(z, G.z0, G.iz, G.gz);
-    const int nb = lane % 27, grp = lane / 27;
-    const int ii = bi + nb % 3 - 1, jj = bj + (nb / 3) % 3 - 1, kk = bk + nb / 9 - 1;
-    const bool inb = lane < 54 && ii >= 0 && ii < G.gx && jj >= 0 && jj < G.gy && kk >= 0 && kk < G.gz;
-    const int b = inb ? (kk * G.gy + jj) * G.gx + ii : 0;
-    // global_ loads (vmcnt only): the scalar loads of the grid's fields below wait on lgkmcnt, which a
-    // flat_ load would hold until these loads are back
-    const int cnt = gload(d.bucket_count + b);
-    CellEntry e[4];
-    int sl[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const CellEntry *ep = d.buckets + b * kBucketCap + grp * 4 + u;
-        e[u].x = gload(&ep->x);
-        e[u].y = gload(&ep->y);
-        e[u].z = gload(&ep->z);
-        e[u].zeta = gload(&ep->zeta);
-        sl[u] = gload(d.bslot + b * kBucketCap + grp * 4 + u);
-    }
-    // every cell outside the 3x3x3 block is at least sqrt(lb) away: computed while the loads fly
-    const double lb = grid_block_lb(G, x, y, z, 1);
-    double bd = kSentinel, bz = 0.0;
-    int bs = -1;
-    bool tie = false;
-    const bool overfull = inb && cnt > 8;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const bool ok = inb && grp * 4 + u < cnt && sl[u] != skip && sl[u] != moved;
-        const double dd = dist2(e[u].x, e[u].y, e[u].z, x, y, z);
-        if (ok) {
-            if (dd < bd) {
-                bd = dd;
-                bs = sl[u];
-                bz = e[u].zeta;
-                tie = false;
-            } else if (dd == bd && dd < kSentinel) {
-                tie = true;
-            }
-        }
-    }
-    if (lane == 63 && moved >= 0) {  // the moved cell, at its proposed site
-        const double dd = dist2(mx, my, mz, x, y, z);
-        if (dd < bd) {
-            bd = dd;
-            bs = moved;
-            bz = mzeta;
-            tie = false;
-        } else if (dd == bd && dd < kSentinel) {
-            tie = true;
-        }
-    }
-    const unsigned long long key = (unsigned long long)__double_as_longlong(bd);
-    const unsigned long long kmin = wave_min_u64(key);
-    const unsigned long long who = __ballot(key == kmin);
-    const int win = __builtin_ctzll(who);
-    Nearest res;
-    res.d = __longlong_as_double((long long)kmin);
-    const bool found = res.d < kSentinel;
-    // distinct slots at the minimum (a slot sits in one lane only), or a tie inside the winner
-    const bool tied = found && (__popcll(who) > 1 || __builtin_amdgcn_readlane((int)tie, win) != 0);
-    const bool any_over = __ballot(overfull) != 0ull;
-    res.s = found ? __builtin_amdgcn_readlane(bs, win) : -1;
-    res.z = found ? readlane_f64(bz, win) : 0.0;
-    res.proven = !ovf && !tied && !any_over && res.d < lb;
-    return res;
-}
-
-// wave_grid_search on the LDS copy of the grid: the same loads, the same answer and the same proof
-// (grid_block_lb's bound, R = 1, each face taken by a select instead of a branch)
-__device__ __forceinline__ Nearest wave_grid_search(const GridGeo &gl, bool ovf, int lane, double x, double y,
-                                                    double z, int skip, int moved, double mx, double my, double mz,
-                                                    double mzeta) {
-    const GridGeo G = gl;  // (one round of LDS loads, every lane the same words)
-    const int bi = grid_axis(x, G.x0, G.ix, G.gx), bj = grid_axis(y, G.y0, G.iy, G.gy),
-              bk = grid_axis(z, G.z0, G.iz, G.gz);
-    const int nb = lane % 27, grp = lane / 27;
-    const int ii = bi + nb % 3 - 1, jj = bj + (nb / 3) % 3 - 1, kk = bk + nb / 9 - 1;
-    const bool inb = lane < 54 && ii >= 0 && ii < G.gx && jj >= 0 && jj < G.gy && kk >= 0 && kk < G.gz;
-    const int b = inb ? (kk * G.gy + jj) * G.gx + ii : 0;
-    const int cnt = gload(G.count + b);
-    CellEntry e[4];
-    int sl[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const CellEntry *ep = G.buckets + b * kBucketCap + grp * 4 + u;
-        e[u].x = gload(&ep->x);
-        e[u].y = gload(&ep->y);
-        e[u].z = gload(&ep->z);
-        e[u].zeta = gload(&ep->zeta);
-        sl[u] = gload(G.bslot + b * kBucketCap + grp * 4 + u);
-    }
-    double bd = kSentinel, bz = 0.0;
-    int bs = -1;
-    bool tie = false;
-    const bool overfull = inb && cnt > 8;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const bool ok = inb && grp * 4 + u < cnt && sl[u] != skip && sl[u] != moved;
-        const double dd = dist2(e[u].x, e[u].y, e[u].z, x, y, z);
-        if (ok) {
-            if (dd < bd) {
-                bd = dd;
-                bs = sl[u];
-                bz = e[u].zeta;
-                tie = false;
-            } else if (dd == bd && dd < kSentinel) {
-                tie = true;
-            }
-        }
-    }
-    if (lane == 63 && moved >= 0) {  // the moved cell, at its proposed site
-        const double dd = dist2(mx, my, mz, x, y, z);
-        if (dd < bd) {
-            bd = dd;
-            bs = moved;
-            bz = mzeta;
-            tie = false;
-        } else if (dd == bd && dd < kSentinel) {
-            tie = true;
-        }
-    }
-    const unsigned long long key = (unsigned long long)__double_as_longlong(bd);
-    const unsigned long long kmin = wave_min_u64_2p(key);
-    const unsigned long long who = __ballot(key == kmin);
-    const int win = __builtin_ctzll(who);
-    Nearest res;
-    res.d = __longlong_as_double((long long)kmin);
-    const bool found = res.d < kSentinel;
-    const bool tied = found && (__popcll(who) > 1 || __builtin_amdgcn_readlane((int)tie, win) != 0);
-    const bool any_over = __ballot(overfull) != 0ull;
-    res.s = found ? __builtin_amdgcn_readlane(bs, win) : -1;
-    res.z = found ? readlane_f64(bz, win) : 0.0;
-    res.proven = !ovf && !tied && !any_over && res.d < G.lb0;
-    if (!res.proven && !ovf && !tied && !any_over) {  // (wave-uniform; rare) the query's own block bound
-        double lb;
-        {
-            const double v[3] = {x, y, z}, e3[3] = {G.ex, G.ey, G.ez};
-            double o2[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {  // grid_out2
-                const double below = G.lo[a] - v[a], above = v[a] - G.hi[a];
-                const double o = (below > above ? below : above) - e3[a];
-                o2[a] = (G.sealed && o > 0.0) ? o * o : 0.0;
-            }
-            lb = __builtin_huge_val();
-            auto face = [&lb](double w, double w0, double h, double e1, int g, int i, double other) {
-                const double gl0 = (w - (w0 + (double)(i - 1) * h)) - e1;
-                const double gh0 = ((w0 + (double)(i + 2) * h) - w) - e1;
-                const double fl = (gl0 > 0.0 ? gl0 * gl0 : 0.0) + other;
-                const double fh = (gh0 > 0.0 ? gh0 * gh0 : 0.0) + other;
-                lb = (i - 1 > 0 && fl < lb) ? fl : lb;
-                lb = (i + 1 < g - 1 && fh < lb) ? fh : lb;
-            };
-            face(x, G.x0, G.hx, G.ex, G.gx, bi, o2[1] + o2[2]);
-            face(y, G.y0, G.hy, G.ey, G.gy, bj, o2[0] + o2[2]);
-            face(z, G.z0, G.hz, G.ez, G.gz, bk, o2[0] + o2[1]);
-            lb = grid_lb_close(lb);
-        }
-        res.proven = res.d < lb;
-    }
-    return res;
-}
-
-// Nearest live cell for one query, one wave: grid first, full scan if unproven.
-__device__ __forceinline__ Nearest wave_nearest(const DevChain &d, const Views &v, Shared &sh, int lane, double x,
-                                                double y, double z, int skip, int moved, double mx, double my,
-                                                double mz, double mzeta) {
-    Nearest r = wave_grid_search(sh.geo, sh.grid_ovf != 0, lane, x, y, z, skip, moved, mx, my, mz, mzeta);
-    if (!r.proven) {
-        if (lane == 0) atomicAdd(&sh.grid_fallbacks32, 1);
-        r = wave_full_scan(d.stamp, d.cx, d.cy, d.cz, d.czeta, d.cap, sh.nslots, lane, x, y, z, skip, moved,
-                           mx, my, mz);
-    }
-    return r;
-}
-
-// Read what the bucket-grid update of an accepted proposal will need (one
-// wave, during phase F, before the decision): the old site's bucket, count,
-// the slot's position in it and its last entry; the new site's bucket and count.
-__device__ void grid_prefetch(const DevChain &d, Shared &sh, int lane, int action, int slot, double ox, double oy,
-                              double oz, double nx, double ny, double nz) {
-    const bool rm = action == tdchain::kDeath || action == tdchain::kMove;
-    const bool ins = action == tdchain::kBirth || action == tdchain::kMove;
-    const bool upd = action == tdchain::kChange;  // the entry's value, in place
-    int bo = 0, co = 0, pos = -1, bn = 0, cn = 0;
-    if (rm || upd) {
-        bo = grid_bucket(d.grid, ox, oy, oz);
-        co = d.bucket_count[bo];
-        const int s = lane < kBucketCap ? d.bslot[bo * kBucketCap + lane] : -1;
-        const unsigned long long m = __ballot(lane < co && s == slot);
-        pos = m ? __builtin_ctzll(m) : -1;
-        if (rm && lane == 0 && co > 0) {
-            sh.gp_last = d.buckets[bo * kBucketCap + co - 1];
-            sh.gp_last_slot = d.bslot[bo * kBucketCap + co - 1];
-        }
-    }
-    if (ins) {
-        bn = grid_bucket(d.grid, nx, ny, nz);
-        cn = d.bucket_count[bn];
-    }
-    if (lane == 0) {
-        sh.gp_bo = bo;
-        sh.gp_co = co;
-        sh.gp_pos = pos;
-        sh.gp_bn = bn;
-        sh.gp_cn = cn;
-    }
-}
-
-// Apply the accepted proposal's bucket-grid update from the prefetched data
-// (lane 0 of one wave; stores only).
-__device__ void grid_apply(const DevChain &d, Shared &sh) {
-    const int op = sh.g_op;
-    int co = sh.gp_co;
-    if (op & 1) {  // remove g_slot: the bucket's last entry takes its place
-        const int b = sh.gp_bo, pos = sh.gp_pos;
-        if (pos < 0) {
-            *d.grid_overflow = 1;  // bookkeeping lost track: stop trusting the grid
-            sh.grid_ovf = 1;
-        } else {
-            d.buckets[b * kBucketCap + pos] = sh.gp_last;
-            d.bslot[b * kBucketCap + pos] = sh.gp_last_slot;
-            d.bucket_count[b] = co - 1;
-            co -= 1;
-        }
-    }
-    if (op & 4) {  // a change: the entry's value
-        const int pos = sh.gp_pos;
-        if (pos < 0) {
-            *d.grid_overflow = 1;
-            sh.grid_ovf = 1;
-        } else {
-            d.buckets[sh.gp_bo * kBucketCap + pos].zeta = sh.g_nzeta;
-        }
-    }
-    if (op & 2) {  // insert at the new site
-        const int b = sh.gp_bn;
-        const int cnt = ((op & 1) && b == sh.gp_bo) ? co : sh.gp_cn;  // a move inside one bucket
-        if (cnt < kBucketCap) {
-            d.buckets[b * kBucketCap + cnt] = CellEntry{sh.g_nx, sh.g_ny, sh.g_nz, sh.g_nzeta};
-            d.bslot[b * kBucketCap + cnt] = sh.g_slot;
-            d.bucket_count[b] = cnt + 1;
-        } else {
-            *d.grid_overflow = 1;
-            sh.grid_ovf = 1;
-        }
-    }
-}
-
-__device__ __forceinline__ void mark(const DevChain &d, const Views &v, Shared &sh, int p, int r, int s, double dd,
-                                     double z) {
-    d.cand_s[p] = s;
-    d.cand_d[p] = dd;
-    d.cand_z[p] = z;
-    d.cand_flag[p] = 1;
-    const int c = atomicAdd(&sh.n_changed, 1);
-    d.changed[c] = p;
-    if (c < kChgLds) sh.chg[c] = ChgRec{p, s, dd, z};
-    if (atomicExch(&v.rflag[r], 1) == 0) {
-        v.ray_put(atomicAdd(&sh.n_rays, 1), r);
-        atomicMin(&sh.k0, r);
-    }
-}
-
-// Tile test in FP32: can some point p of tile t have dist2(q, p) <= thr?
-// Every rounding is taken against the answer (the query rounded to FP32 moves
-// by <= |q| 2^-24, each FP32 operation errs by <= 2^-24 relative), so the test
-// never says "no" for a tile that holds such a point; it may say "yes" for a
-// tile that does not (its points are then checked exactly in FP64).
-struct TileQuery {
-    float x, y, z, ex, ey, ez;  // coordinates and their rounding allowance
-};
-__device__ __forceinline__ TileQuery tile_query(double x, double y, double z) {
-    TileQuery q;
-    q.x = (float)x;
-    q.y = (float)y;
-    q.z = (float)z;
-    q.ex = fabsf(q.x) * 0x1p-23f;
-    q.ey = fabsf(q.y) * 0x1p-23f;
-    q.ez = fabsf(q.z) * 0x1p-23f;
-    return q;
-}
-__device__ __forceinline__ float gap_lb(float q, float e, float l, float h) {
-    const float g = fmaxf(fmaxf(l - q, q - h), 0.0f);
-    return fmaxf(g * (1.0f - 0x1p-20f) - e, 0.0f);
-}
-// thr: an FP32 bound >= the FP64 threshold (tile_thr)
-__device__ __forceinline__ bool tile_may_hit(const float *lo, const float *hi, int nt, int t, const TileQuery &q,
-                                             float thr) {
-    const float gx = gap_lb(q.x, q.ex, lo[t], hi[t]);
-    const float gy = gap_lb(q.y, q.ey, lo[nt + t], hi[nt + t]);
-    const float gz = gap_lb(q.z, q.ez, lo[2 * nt + t], hi[2 * nt + t]);
-    float s = gx * gx;
-    s = s + gy * gy;
-    s = s + gz * gz;
-    return s * (1.0f - 0x1p-20f) <= thr;
-}
-__device__ __forceinline__ float tile_thr(double mx) { return (float)mx * (1.0f + 0x1p-20f); }
-
-// The same filter in about half the VALU operations (phase B's tile pass, LDS layout; TD_TILE2): the
-// query's rounding folded into two per-query bounds per axis, one max3 per axis, the squares summed with
-// FMAs.  Never says "no" for a tile holding a point p with dist2(q, p) <= mx (FP64), thr = tile_thr(mx):
-// with E = max_a |(float)q_a| 2^-23 >= |q_a - (float)q_a| on every axis, up = fl((float)q + 2E) >= q and
-// dn = fl((float)q - 2E) <= q (the rounding of the add is at most E/2); for p in the outward-rounded box,
-// |p_a - q_a| >= max(lo - up, dn - hi, 0) >= g_a (1 - 2^-24) with g_a the rounded max3; the FMA sum s
-// errs by at most 3 ulps, so the real sum of the squared gaps -- a lower bound of the exact squared
-// distance, itself within 2^-50 of the FP64 one -- is >= s (1 - 2^-21); and thr >= mx (1 - 2^-24)^2
-// (1 + 2^-20), so s > thr implies dist2(q, p) > mx for every point of the tile.
-#ifndef TD_TILE2
-#define TD_TILE2 1
-#endif
-struct TileQuery2 {
-    float ux, uy, uz, dx, dy, dz;  // the query's upper and lower bounds per axis
-};
-__device__ __forceinline__ TileQuery2 tile_query2(double x, double y, double z) {
-    const float fx = (float)x, fy = (float)y, fz = (float)z;
-    const float e2 = fmaxf(fmaxf(fabsf(fx), fabsf(fy)), fabsf(fz)) * 0x1p-22f;  // 2E
-    return TileQuery2{fx + e2, fy + e2, fz + e2, fx - e2, fy - e2, fz - e2};
-}
-struct TileBox {
-    float lx, ly, lz, hx, hy, hz, thr;
-};
-__device__ __forceinline__ TileBox tile_box(const float *lo, const float *hi, const double *maxd, int nt, int t) {
-    return TileBox{lo[t], lo[nt + t], lo[2 * nt + t], hi[t], hi[nt + t], hi[2 * nt + t], tile_thr(maxd[t])};
-}
-__device__ __forceinline__ bool tile_may_hit2(const TileBox &b, const TileQuery2 &q) {
-    const float gx = fmaxf(fmaxf(b.lx - q.ux, q.dx - b.hx), 0.0f);
-    const float gy = fmaxf(fmaxf(b.ly - q.uy, q.dy - b.hy), 0.0f);
-    const float gz = fmaxf(fmaxf(b.lz - q.uz, q.dz - b.hz), 0.0f);
-    float s = gx * gx;
-    s = __builtin_fmaf(gy, gy, s);
-    s = __builtin_fmaf(gz, gz, s);
-    return s <= b.thr;
-}
-// x rounded up to FP32 (x >= 0; the super-tile maxima)
-__device__ __forceinline__ float f32_up(double x) {
-    const float f = (float)x;
-    return (double)f < x ? __int_as_float(__float_as_int(f) + 1) : f;  // f >= 0 finite: the next float up
-}
-
-// System-scope access to the mailbox (pinned host memory, the host polls it)
-__device__ __forceinline__ long long mb_load(const long long *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ void mb_store(long long *p, long long v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// Server mode, wave 0: wait for the next EVAL or QUIT command, answering
-// QUERY commands (one-point Interpolation on the committed model or the model
-// plus one edit -- the state here is the committed one, a pending proposal
-// lives only in the candidate overlay) meanwhile.  EVAL: its steps into
-// sh.srv_*, the pending proposal's fate into sh.gs.accept; QUIT or silence:
-// sh.srv_quit (and undo).
-__device__ void server_wait(Mailbox *mb, const DevChain &d, const Views &v, Shared &sh, int lane) {
-    constexpr int kWords = (int)(offsetof(Mailbox, done) / sizeof(long long));
-    static_assert(kWords <= 64 && kWords <= (int)(sizeof(sh.mbox) / sizeof(long long)), "mailbox payload");
-    long long seen = sh.srv_seq;
-    long long t0 = (long long)wall_clock64();
-    if (lane == 0 && sh.srv_busy_c) {  // diagnostic: the busy interval that ends here (clock rate)
-        mb_store(&mb->diag[0], clock64() - sh.srv_busy_c);
-        mb_store(&mb->diag[1], t0 - sh.srv_busy_w);
-    }
-    static_assert(kMailboxCheckWord == kWords - 1, "the check is the command's last word");
-    long long polls = 0;
-    while (true) {
-        // every poll reads the whole command, one word per lane (as cheap as seq alone: one round
-        // trip); a new seq is taken only with a matching check -- the poll may have caught the
-        // host between its words (then the next poll reads them again)
-        // (no system-scope acquire: the command is read through system-scope atomics, and one
-        // would invalidate this XCD's L2, the chain's working set, at every call)
-        const long long w = lane < kWords ? mb_load(reinterpret_cast<const long long *>(mb) + lane) : 0;
-        const long long sq = (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(w >> 32), 0) << 32) |
-                                         (unsigned)__builtin_amdgcn_readlane((int)w, 0));
-        ++polls;
-        bool fresh = sq != seen;
-        if (fresh) {  // (a torn read: not yet -- the next poll reads the words again)
-            const unsigned long long h =
-                wave_xor_u64(lane >= 1 && lane < kWords - 1 ? mailbox_word_mix((unsigned long long)w, lane, sq) : 0ull);
-            const unsigned long long chk =
-                ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(w >> 32), kWords - 1) << 32) |
-                (unsigned)__builtin_amdgcn_readlane((int)w, kWords - 1);
-            fresh = h == chk;
-        }
-        if (fresh) {
-            seen = sq;
-            if (lane == 0) {
-                sh.srv_busy_c = clock64();
-                sh.srv_busy_w = (long long)wall_clock64();
-                mb_store(&mb->diag[2], polls);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            if (lane < kWords) sh.mbox[lane] = w;
-            wave_sync_lds();
-            const Mailbox &c = *reinterpret_cast<const Mailbox *>(sh.mbox);
-            if (c.type == kCmdQuery) {
-                const double x = c.q[0], y = c.q[1], z = c.q[2];
-                const bool has_edit = c.has_edit != 0;
-                const ScriptStep e = c.qedit;
-                int skip = -1, moved = -1, slot_k = -1;
-                if (has_edit && e.action != tdchain::kBirth) slot_k = v.ord[e.index];
-                if (has_edit && e.action == tdchain::kDeath) skip = slot_k;  // the reduced model (:132-135)
-                if (has_edit && e.action == tdchain::kMove) moved = slot_k;  // the cell at its new site
-                const Nearest r = wave_nearest(d, v, sh, lane, x, y, z, skip, moved, e.x, e.y, e.z,
-                                               moved >= 0 ? d.czeta[moved] : 0.0);
-                double val = r.z;
-                if (has_edit && e.action == tdchain::kChange && r.s == slot_k) val = e.zeta;
-                if (has_edit && e.action == tdchain::kBirth) {  // the appended cell wins only strictly (last position)
-                    const double dd = dist2(e.x, e.y, e.z, x, y, z);
-                    if (dd < r.d && dd < kSentinel) val = e.zeta;
-                }
-                if (lane == 0) {
-                    mb_store(reinterpret_cast<long long *>(&mb->qval), __double_as_longlong(val));
-                    __builtin_amdgcn_s_waitcnt(0);  // the answer acknowledged before done (no L2 write-back)
-                    mb_store(&mb->done, sq);
-                }
-                wave_sync_lds();
-                t0 = (long long)wall_clock64();
-                continue;
-            }
-            if (lane == 0) {
-                sh.srv_seq = sq;
-                if (c.type == kCmdEval) {
-                    const int ns = min(max(c.nsteps, 1), kMaxScript);
-                    for (int k = 0; k < ns; ++k) sh.srv_step[k] = c.step[k];
-                    sh.srv_n = ns;
-                    sh.srv_k = 0;
-                    sh.gs.accept = c.decision != 0 ? 1 : 0;
-                    sh.srv_quit = 0;
-                } else {  // quit: the pending proposal (if any) is undone
-                    sh.gs.accept = 0;
-                    sh.srv_quit = 1;
-                }
-            }
-            wave_sync_lds();
-            return;
-        }
-        if ((long long)wall_clock64() - t0 > kServerIdleTicks) {  // no host: undo and return
-            if (lane == 0) {
-                sh.gs.accept = 0;
-                sh.srv_quit = 1;
-            }
-            wave_sync_lds();
-            return;
-        }
-        __builtin_amdgcn_s_sleep(2);
-    }
-}
-
-// Resident tempering rounds, wave 0 at a round boundary: publish the chain's
-// phi for the round just finished (done = its seq), then wait for the next
-// command: RUN (K proposals at the slot's new temperature) or QUIT; silence
-// past the idle watchdog is a QUIT (the state is consistent between rounds).
-// Results in sh.rK / sh.rT / sh.rinv2t / sh.srv_quit.
-// A RUN posted with the slot's `skip` set (the chain ran that round in a launch
-// the host lost, chain.cpp td_rounds_run) is answered with phi at once and
-// waited past: the chain runs each round exactly once.  `phi` = the chain's
-// exact phi (the launch's first wait: its stored one).
-__device__ void round_wait(RoundBox *rb, int b, Shared &sh, int lane, bool publish, double phi) {
-    RoundSlot *slot = &rb->slot[b];
-    // The mailbox is coherent pinned host memory and every access to it is a system-scope atomic,
-    // so no system-scope fence is needed -- one would write back (release) or invalidate (acquire)
-    // this XCD's whole L2, the chain's working set, at every round.  phi is acknowledged before
-    // done is written (the host reads done, then phi).
-    if (publish && lane == 0) {
-        mb_store(reinterpret_cast<long long *>(&slot->phi), __double_as_longlong(phi));
-        __builtin_amdgcn_s_waitcnt(0);
-        mb_store(&slot->done, sh.rseq);
-    }
-    long long seen = sh.rseq;
-    long long idle = kServerIdleTicks;
-    if (!publish) {  // a launch's first wait: the testing override of the watchdog
-        const long long o = mb_load(&slot->idle);
-        if (o > 0) idle = o;
-    }
-    long long t0 = (long long)wall_clock64();
-    while (true) {
-        const long long sq = mb_load(&rb->seq);
-        if (sq != seen) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            if (lane == 0) {
-                // (the host wrote them before seq: four loads in flight together)
-                const long long w = mb_load(reinterpret_cast<const long long *>(rb) + 1);  // cmd | K << 32
-                const long long tb = mb_load(reinterpret_cast<const long long *>(&slot->T));
-                const long long ib = mb_load(reinterpret_cast<const long long *>(&slot->inv_2t));
-                const long long sk = mb_load(&slot->skip);
-                const int cmd = (int)(w & 0xffffffffll), K = (int)(w >> 32);
-                sh.rseq = sq;
-                sh.rskip = 0;
-                if (cmd == kRoundRun && K > 0 && sk) {  // ran already: report it again
-                    mb_store(reinterpret_cast<long long *>(&slot->phi), __double_as_longlong(phi));
-                    __builtin_amdgcn_s_waitcnt(0);
-                    mb_store(&slot->done, sq);
-                    sh.rskip = 1;
-                } else if (cmd == kRoundRun && K > 0) {
-                    sh.rK = K;
-                    sh.rT = __longlong_as_double(tb);
-                    sh.rinv2t = __longlong_as_double(ib);
-                    sh.srv_quit = 0;
-                } else {
-                    sh.srv_quit = 1;
-                }
-            }
-            wave_sync_lds();
-            if (sh.rskip) {
-                seen = sq;
-                t0 = (long long)wall_clock64();
-                continue;
-            }
-            return;
-        }
-        if ((long long)wall_clock64() - t0 > idle) {
-            if (lane == 0) sh.srv_quit = 1;
-            wave_sync_lds();
-            return;
-        }
-        __builtin_amdgcn_s_sleep(2);
-    }
-}
-
-// Exchange rounds (chain_dev.h RoundX), wave 0 at the end of round j with the
-// chain's exact phi: publish it, wait for every replica's phi of the round,
-// make the round's swap decisions (all of them, the same in every workgroup
-// of every rank: chain_logic.h swap_accept on the gathered vector) and take
-// this chain's new temperature (sh.rT, sh.rinv2t).  sh.srv_quit = 1 when an
-// exchange never came (x.err set).  R <= 64: lane g holds replica g.
-__device__ void round_exchange(const RoundX &x, int b, long long j, Shared &sh, int lane, double phi) {
-    const int R = x.R;
-    const unsigned long long tag = x.ready_base + (unsigned long long)j + 1ull;
-    if (b == 0 && lane == 0) x.log_t[3 * j] = (long long)wall_clock64();
-    if (lane == 0) {  // phi acknowledged before the flag (the readers load the flag, then phi)
-        mb_store(reinterpret_cast<long long *>(&x.xin[(j & 1) * x.local + b]), __double_as_longlong(phi));
-        __builtin_amdgcn_s_waitcnt(0);
-        mb_store(reinterpret_cast<long long *>(&x.rdy[b]), (long long)tag);
-    }
-    const bool one = x.gdone == nullptr;  // one rank: xout is xin, every replica's flag is local
-    const int nflags = one ? R : x.local;
-    bool ok = true;
-    if (one || b == 0) {  // wait for the flags (lane g reads flag g)
-        const long long t0 = (long long)wall_clock64();
-        while (true) {
-            const unsigned long long f =
-                lane < nflags ? (unsigned long long)mb_load(reinterpret_cast<const long long *>(&x.rdy[lane])) : tag;
-            if (__all(f >= tag)) break;
-            if ((long long)wall_clock64() - t0 > kExchangeTicks) {
-                ok = false;
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-        if (!one && ok && lane == 0)  // this rank's phis are in: the exchange stream may gather
-            mb_store(reinterpret_cast<long long *>(x.ready), (long long)tag);
-        if (b == 0 && lane == 0) x.log_t[3 * j + 1] = (long long)wall_clock64();
-    }
-    if (!one && ok) {  // the allgather of round j done (the exchange stream's write)
-        const unsigned long long want = x.gdone_base + (unsigned long long)j + 1ull;
-        const long long t0 = (long long)wall_clock64();
-        while ((unsigned long long)mb_load(reinterpret_cast<const long long *>(x.gdone)) < want) {
-            if ((long long)wall_clock64() - t0 > kExchangeTicks) {
-                ok = false;
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-    }
-    if (!ok) {
-        if (lane == 0) {
-            mb_store(x.err, 1ll);
-            sh.srv_quit = 1;
-        }
-        wave_sync_lds();
-        return;
-    }
-    if (b == 0 && lane == 0) x.log_t[3 * j + 2] = (long long)wall_clock64();
-    // every replica's phi and level (system-scope loads: the gathered vector bypasses the L2s)
-    const bool in = lane < R;
-    const double ph =
-        in ? __longlong_as_double(mb_load(reinterpret_cast<const long long *>(&x.xout[(j & 1) * R + lane]))) : 0.0;
-    const int lv = in ? x.lev[b * R + lane] : lane;
-    // owner of level l (lane l): the replica at that level -- a forward permute of the levels
-    const int owner = __builtin_amdgcn_ds_permute(lv * 4, lane);
-    const unsigned long long rnd = (unsigned long long)(x.rnd0 + j);
-    const int par = (int)(rnd & 1ull);
-    // pair leaders l = par, par + 2, ... < R - 1 decide the disjoint pairs (l, l + 1)
-    const bool leader = lane >= par && ((lane - par) & 1) == 0 && lane + 1 < R;
-    const int owner_hi = __shfl(owner, (lane + 1) & 63);
-    const double pa = __shfl(ph, owner & 63), pb = __shfl(ph, owner_hi & 63);
-    bool acc = false;
-    if (leader) acc = tdchain::swap_accept(pa, pb, x.temps[lane], x.temps[lane + 1], x.seed, rnd, (uint64_t)lane);
-    // every replica: its pair (led by its level, or by the level below) and that pair's fate
-    int lead = -1;
-    if (in) {
-        if (lv >= par && ((lv - par) & 1) == 0 && lv + 1 < R) lead = lv;
-        else if (lv - 1 >= par && ((lv - 1 - par) & 1) == 0) lead = lv - 1;
-    }
-    const int acc_i = __shfl((int)acc, lead < 0 ? 0 : lead);
-    const int nl = (lead >= 0 && acc_i) ? (lv == lead ? lead + 1 : lead) : lv;
-    if (in) {
-        x.lev[b * R + lane] = nl;
-        if (b == 0) {
-            x.log_phi[j * R + lane] = ph;
-            x.log_lev[j * R + lane] = nl;
-        }
-    }
-    const int me = x.rank * x.local + b;
-    const int my_level = __shfl(nl, me);
-    if (lane == 0) {
-        const double T = x.temps[my_level];
-        sh.rT = T;
-        sh.rinv2t = 1.0 / (2.0 * T);  // = params_derived's inv_2t
-    }
-    wave_sync_lds();
-}
-
-// One array of a fused block copy: U elements per thread per round, loaded
-// into registers by load(), written by store().  Several Segs loaded before
-// any is stored keep all their loads in flight at once: the launch preamble
-// is a handful of memory round trips whatever the number of arrays.  S = the
-// block's thread count (the caller's loop steps by U * S).
-template <class T, int U, int S = kChainThreads>
-struct CopySeg {
-    T *dst;
-    const T *src;
-    int n;
-    T v[U];
-    __device__ __forceinline__ void load(int b) {
-        if (n <= 0) return;
-#pragma unroll
-        for (int u = 0; u < U; ++u) v[u] = src[min(b + u * S, n - 1)];
-    }
-    __device__ __forceinline__ void store(int b) {
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-            if (b + u * S < n) dst[b + u * S] = v[u];
-    }
-};
 
 // The decisions on bounds (phase F): 2u, u = 2^-53 the unit roundoff -- every rounding bound below is
 // taken twice over
@@ -1266,29 +213,6 @@ __device__ __attribute__((noinline)) ExactPhis exact_sums(const double *term, do
         phi_n = wave_seq_sum(term + k0, n - k0, k0 > 0 ? prefix[k0 - 1] : 0.0, cprefix + k0, lane, nullptr, &stopped);
     }
     return ExactPhis{phi, phi_n};
-}
-
-// A scripted step's answer in the pinned output (wave 0; system-scope stores): [phi, k, (ray, ptS) x k],
-// the changed rays' new t* (the caller holds the model's ptS); k = -1: the whole proposed ptS follows.
-// phi: NaN when the answer goes out before phase F (a server's step: the host forms phi_n itself).
-__device__ void server_report(double *outp, const Views &v, const Shared &sh, int n, int lane, double phi) {
-    long long *out = reinterpret_cast<long long *>(outp);
-    auto put = [&](int i, double x) { mb_store(out + i, __double_as_longlong(x)); };
-    const int nr = sh.n_rays;
-    const bool few = 2 * nr + 2 <= n + 1;
-    if (few) {
-        for (int i = lane; i < nr; i += 64) {
-            const int r = v.ray_at(i);
-            put(2 + 2 * i, (double)r);
-            put(3 + 2 * i, v.cptS[r]);
-        }
-    } else {
-        for (int r = lane; r < n; r += 64) put(2 + r, v.rflag[r] ? v.cptS[r] : v.ptS[r]);
-    }
-    if (lane == 0) {
-        put(0, phi);
-        put(1, few ? (double)nr : -1.0);
-    }
 }
 
 // One sample of a recorded launch (RecDesc, chain_dev.h), by the whole block right after the
@@ -1351,6 +275,13 @@ __device__ __attribute__((noinline)) void record_sample(const DevChain &d, const
     }
 }
 
+// ---------------------------------------------------------------- k_chain_run ----
+// The body below is one function on purpose, and is changed only with a comparison of the generated
+// assembly of all 12 instances and a same-machine A/B: every instance sits at 256 VGPRs with 976-1280 B
+// per lane of scratch, and its register allocation moves with any restructuring -- wrapping only the
+// mirror preamble in an always-inlined lambda changed the allocation of every LDS-layout instance
+// (scratch +16 B/lane in two, spill counts up in three and down in two).  So no phase is extracted and
+// no local renamed; code that can live outside it does (the headers above).
 // SCRIPT: host-given proposals (td_evaluate's incremental path: scripted
 // steps, the resident server); a free-running chain's instance has none of
 // that code on its path.
@@ -2887,6 +1818,9 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
 }
 
 // ------------------------------------------------- one-point queries ----
+// (In this unit because k_chain_run's generated code depends on it: the device code of a unit is
+// optimised as one module, and without this second caller of wave_nearest in it the grid search inlined
+// into every k_chain_run instance, and server_wait, come out with other instructions.)
 // Interpolation at one point (MCsub.jl:306-327 with 1-element X/Y/Z, as the
 // reference's birth and death queries call it, TD_inversion_function.jl:81,
 // 146) against a chain's committed model, or that model plus one edit
@@ -2921,277 +1855,7 @@ __global__ __launch_bounds__(64) void k_chain_query(const DevChain *__restrict__
     if (lane == 0) out[0] = val;
 }
 
-// ------------------------------------------------------------ full state ----
-// chi^2 prefix sums, sequential (MCsub.jl:170-172), and phi.
-__global__ __launch_bounds__(256) void k_chi2_prefix(const double *__restrict__ ptS, const double *__restrict__ tS,
-                                                     const double *__restrict__ sig, int n,
-                                                     double *__restrict__ prefix, ChainScalars *st) {
-    __shared__ double t[2048];
-    double C = 0.0;
-    for (int base = 0; base < n; base += 2048) {
-        const int cnt = min(2048, n - base);
-        for (int k = threadIdx.x; k < cnt; k += 256) {
-            const double df = ptS[base + k] - tS[base + k];
-            const double sg = sig[base + k];
-            t[k] = ((df * df) * 1.0) / (sg * sg);
-        }
-        __syncthreads();
-        if (threadIdx.x == 0)
-            for (int k = 0; k < cnt; ++k) {
-                C = C + t[k];
-                prefix[base + k] = C;
-            }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) st->phi = C;
-}
-
-__global__ void k_tile_max(const int *__restrict__ tile_start, int ntiles, const double *__restrict__ best_d,
-                           double *__restrict__ tile_maxd) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= ntiles) return;
-    double mx = -1.0;
-    const int sc = tile_start[t];  // start << 5 | count
-    for (int q = sc >> 5; q < (sc >> 5) + (sc & 31); ++q) mx = fmax(mx, best_d[q]);
-    tile_maxd[t] = mx;
-}
-
-// The proposal-time chi^2 of phase F on a caller-given ptS (testing): terms as
-// phase E writes them, the one-wave exact scan from k0 = 0 and from k0 = n/2
-// (C0 = the sequential prefix[k0 - 1] of k_chi2_prefix).
-__global__ __launch_bounds__(64) void k_test_chain_chi2(const double *__restrict__ ptS, const double *__restrict__ tS,
-                                                        const double *__restrict__ sig, int n,
-                                                        const double *__restrict__ prefix, double *term,
-                                                        double *cprefix, double *out) {
-    const int lane = threadIdx.x;
-    for (int r = lane; r < n; r += 64) {
-        const double df = ptS[r] - tS[r];
-        const double sg = sig[r];
-        term[r] = ((df * df) * 1.0) / (sg * sg);  // MCsub.jl:171
-    }
-    __syncthreads();
-    bool stopped = false;
-    const double a = wave_seq_sum(term, n, 0.0, cprefix, lane, nullptr, &stopped);
-    const int k0 = n / 2;
-    stopped = false;
-    const double b = k0 < n ? wave_seq_sum(term + k0, n - k0, k0 > 0 ? prefix[k0 - 1] : 0.0, cprefix + k0, lane, nullptr,
-                                           &stopped)
-                            : a;
-    if (lane == 0) {
-        out[0] = a;
-        out[1] = b;
-    }
-}
-
 }  // namespace
-
-hipError_t test_chain_chi2(const double *ptS, const double *tS, const double *sig, int n, int path, double *scratch,
-                           double *out, hipStream_t s) {
-    if (n < 1 || n > 4096) return hipErrorInvalidValue;
-    double *prefix = scratch, *term = scratch + n, *cpre = scratch + 2 * n;
-    ChainScalars *st = reinterpret_cast<ChainScalars *>(scratch + 3 * n + 8);  // 16-byte aligned slot
-    static_assert(sizeof(ChainScalars) <= 1024, "scratch slot");
-    if (path == 2) {
-        hipLaunchKernelGGL(k_chi2_prefix, dim3(1), dim3(256), 0, s, ptS, tS, sig, n, prefix, st);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        return hipMemcpyAsync(out, &st->phi, sizeof(double), hipMemcpyDeviceToDevice, s);
-    }
-    hipLaunchKernelGGL(k_chi2_prefix, dim3(1), dim3(256), 0, s, ptS, tS, sig, n, prefix, st);
-    hipLaunchKernelGGL(k_test_chain_chi2, dim3(1), dim3(64), 0, s, ptS, tS, sig, n, prefix, term, cpre, out);
-    return hipGetLastError();
-}
-
-hipError_t chain_full_state(DevChain &d, int ncells, NNWork &work, int num_cus, hipStream_t s) {
-    Geometry g;
-    g.m = 0;
-    g.n = d.n;
-    g.P = d.P;
-    g.px = const_cast<double *>(d.px);
-    g.py = const_cast<double *>(d.py);
-    g.pz = const_cast<double *>(d.pz);
-    g.w = const_cast<double *>(d.w);
-    g.ray_off = const_cast<int *>(d.ray_off);
-    g.tS = const_cast<double *>(d.tS);
-    g.sig = const_cast<double *>(d.sig);
-    // slots 0..ncells-1 hold the cells in order, so nearest index == slot
-    hipError_t e = launch_nearest(d.px, d.py, d.pz, d.P, 1, 1, d.cx, d.cap, ncells, work, num_cus, d.best_s,
-                                  d.best_d, d.zeta0, s);
-    if (e != hipSuccess) return e;
-    e = launch_ray_sums(g, d.zeta0, d.ptS, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_chi2_prefix, dim3(1), dim3(256), 0, s, d.ptS, d.tS, d.sig, d.n, d.prefix, d.st);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (d.ntiles > 0) {
-        hipLaunchKernelGGL(k_tile_max, dim3((d.ntiles + 255) / 256), dim3(256), 0, s, d.tile_start, d.ntiles,
-                           d.best_d, d.tile_maxd);
-        e = hipGetLastError();
-    }
-    return e;
-}
-
-// Testing: the latency of a nearest-cell query through the chain's bucket grid, as phases B and D run
-// it: one wave answers nq queries back to back, each point offset by 0 * the previous answer (no two
-// overlap).  mode 0: wave_nearest; 1: its loads only (the sum of what they bring); 2: its arithmetic only
-// (the loads replaced by values made from the lane).  out[0] = cycles, out[1] = unproven queries.
-__global__ __launch_bounds__(64) void k_test_query_lat(const DevChain *__restrict__ dptr, const double *__restrict__ pts,
-                                                        int nq, int mode, long long *out) {
-    __shared__ Shared sh;
-    const DevChain &d = *dptr;
-    const int lane = threadIdx.x;
-    Views v{};
-    v.ord = d.order;
-    if (lane == 0) {
-        sh.grid_ovf = *d.grid_overflow;
-        sh.grid_fallbacks32 = 0;
-        sh.nslots = d.st->nslots;
-        geo_fill(sh.geo, d);
-    }
-    __syncthreads();
-    double acc = 0.0;
-    unsigned long long hsh = 0xcbf29ce484222325ull;
-    const long long t0 = clock64();
-    for (int i = 0; i < nq; ++i) {
-        const double k = acc * 0.0;
-        const double x = pts[3 * i] + k, y = pts[3 * i + 1] + k, z = pts[3 * i + 2] + k;
-        if (mode == 0 || mode == 6) {  // 6: the descriptor-reading search (d.grid), for comparison
-            const Nearest r = mode == 0 ? wave_grid_search(sh.geo, sh.grid_ovf != 0, lane, x, y, z, -1, -1, 0.0, 0.0,
-                                                           0.0, 0.0)
-                                        : wave_grid_search(d, sh.grid_ovf != 0, lane, x, y, z, -1, -1, 0.0, 0.0,
-                                                           0.0, 0.0);
-            acc = r.z;
-            // (a digest of every answer: the two searches must agree)
-            hsh = hsh * 0x100000001b3ull ^ (unsigned long long)__double_as_longlong(r.d) ^
-                  ((unsigned long long)(unsigned)r.s << 1) ^ (unsigned long long)r.proven;
-        } else {
-            const CellGrid &G = d.grid;
-            const int bi = grid_axis(x, G.x0, G.ix, G.gx), bj = grid_axis(y, G.y0, G.iy, G.gy),
-                      bk = grid_axis(z, G.z0, G.iz, G.gz);
-            const int nb = lane % 27, grp = lane / 27;
-            const int ii = bi + nb % 3 - 1, jj = bj + (nb / 3) % 3 - 1, kk = bk + nb / 9 - 1;
-            const bool inb = lane < 54 && ii >= 0 && ii < G.gx && jj >= 0 && jj < G.gy && kk >= 0 && kk < G.gz;
-            const int b = inb ? (kk * G.gy + jj) * G.gx + ii : 0;
-            double t = 0.0;
-            if (mode == 3) {  // the bucket indices alone
-                t = (double)(b + grp);
-            } else if (mode == 4) {  // the block's face bound alone
-                t = grid_block_lb(G, x, y, z, 1);
-            } else if (mode == 5) {  // one lexicographic wave minimum alone
-                t = (double)wave_min_u64((unsigned long long)(b + lane));
-            } else if (mode == 1) {
-                const int cnt = gload(d.bucket_count + b);
-                double a = 0.0;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const CellEntry *ep = d.buckets + b * kBucketCap + grp * 4 + u;
-                    a = a + gload(&ep->x) + gload(&ep->y) + gload(&ep->z) + gload(&ep->zeta) +
-                        (double)gload(d.bslot + b * kBucketCap + grp * 4 + u);
-                }
-                t = a + (double)cnt;
-                t = wave_sum_f64(t);
-            } else {
-                double bd = kSentinel;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const double dd = dist2((double)b, (double)u, (double)lane, x, y, z);
-                    bd = dd < bd ? dd : bd;
-                }
-                const double lb = grid_block_lb(G, x, y, z, 1);
-                const unsigned long long kmin = wave_min_u64((unsigned long long)__double_as_longlong(bd));
-                t = __longlong_as_double((long long)kmin) < lb ? 1.0 : 2.0;
-            }
-            acc = t;
-        }
-    }
-    const long long t1 = clock64();
-    if (lane == 0) {
-        out[0] = t1 - t0;
-        out[1] = sh.grid_fallbacks32;
-        out[2] = __double_as_longlong(acc);
-        out[3] = (long long)hsh;
-    }
-}
-
-// Testing: every query's answer (squared distance, the winning cell's value, proven) from the chain's grid
-// search, mode 0 (the LDS GridGeo copy with the global first bound) or 6 (the descriptor-reading form):
-// the tests compare the proven ones with an exact scan (tdt_chain_query_answers)
-__global__ __launch_bounds__(64) void k_test_query_answers(const DevChain *__restrict__ dptr, const double *__restrict__ pts,
-                                                           int nq, int mode, double *out_d, double *out_z, int *out_p) {
-    __shared__ Shared sh;
-    const DevChain &d = *dptr;
-    const int lane = threadIdx.x;
-    if (lane == 0) {
-        sh.grid_ovf = *d.grid_overflow;
-        sh.grid_fallbacks32 = 0;
-        geo_fill(sh.geo, d);
-    }
-    __syncthreads();
-    for (int i = 0; i < nq; ++i) {
-        const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-        const Nearest r = mode == 0 ? wave_grid_search(sh.geo, sh.grid_ovf != 0, lane, x, y, z, -1, -1, 0.0, 0.0, 0.0, 0.0)
-                                    : wave_grid_search(d, sh.grid_ovf != 0, lane, x, y, z, -1, -1, 0.0, 0.0, 0.0, 0.0);
-        if (lane == 0) {
-            out_d[i] = r.d;
-            out_z[i] = r.z;
-            out_p[i] = r.proven ? 1 : 0;
-        }
-    }
-}
-
-// Testing: the phase-B tile filter on given FP32 boxes (SoA, 3 x nt each), FP64 tile maxima and FP64
-// queries: out[q * nt + t] = 1 if the filter lets tile t through for query q (mode 0 tile_may_hit, 1
-// tile_may_hit2).  The tests hold it to "never drops a tile holding a point within the maximum".
-__global__ void k_test_tile_filter(const float *__restrict__ lo, const float *__restrict__ hi,
-                                   const double *__restrict__ maxd, int nt, const double *__restrict__ qs, int nq,
-                                   int mode, unsigned char *__restrict__ out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)nt * nq) return;
-    const int t = (int)(i % nt), q = (int)(i / nt);
-    const double x = qs[3 * q], y = qs[3 * q + 1], z = qs[3 * q + 2];
-    bool h;
-    if (mode == 0) {
-        h = tile_may_hit(lo, hi, nt, t, tile_query(x, y, z), tile_thr(maxd[t]));
-    } else {
-        h = tile_may_hit2(tile_box(lo, hi, maxd, nt, t), tile_query2(x, y, z));
-    }
-    out[i] = h ? 1 : 0;
-}
-
-hipError_t test_tile_filter(const float *lo, const float *hi, const double *maxd, int nt, const double *qs, int nq,
-                            int mode, unsigned char *out, hipStream_t s) {
-    const long long n = (long long)nt * nq;
-    hipLaunchKernelGGL(k_test_tile_filter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, lo, hi, maxd, nt, qs,
-                       nq, mode, out);
-    return hipGetLastError();
-}
-
-hipError_t test_query_answers(const DevChain *dev, const double *pts, int nq, int mode, double *out_d, double *out_z,
-                              int *out_p, hipStream_t s) {
-    hipLaunchKernelGGL(k_test_query_answers, dim3(1), dim3(64), 0, s, dev, pts, nq, mode, out_d, out_z, out_p);
-    return hipGetLastError();
-}
-
-hipError_t test_query_lat(const DevChain *dev, const double *pts, int nq, int mode, long long *out, hipStream_t s) {
-    hipLaunchKernelGGL(k_test_query_lat, dim3(1), dim3(64), 0, s, dev, pts, nq, mode, out);
-    return hipGetLastError();
-}
-
-hipError_t chain_query(const DevChain *dev, double x, double y, double z, const ScriptStep *edit, double *out,
-                       hipStream_t s) {
-    ScriptStep e{};
-    if (edit) e = *edit;
-    hipLaunchKernelGGL(k_chain_query, dim3(1), dim3(64), 0, s, dev, x, y, z, e, edit ? 1 : 0, out);
-    return hipGetLastError();
-}
-
-void chain_lds_sizes(const DevChain &d, int64_t out[4]) {
-    const LdsPlan a = lds_plan(d.ntiles, d.n, d.cap, true), b = lds_plan(d.ntiles, d.n, d.cap, false);
-    out[0] = (int64_t)a.total;      // LDS layout (tiles, rays, order mirrored)
-    out[1] = (int64_t)b.total;      // HBM layout
-    out[2] = b.super_lds ? 1 : 0;   // HBM layout with super-tiles in LDS
-    out[3] = (int64_t)(a.total <= kLdsBudget && d.lds_mode != 1);  // the layout a launch takes: 1 = LDS
-}
 
 // Every iteration's draws of a launch (a function of seed, chain, iteration: tdchain::draw_iteration),
 // one thread each, ahead of k_chain_run: its per-64-iteration refill -- one wave computing 64 draws'
@@ -3204,16 +1868,51 @@ __global__ __launch_bounds__(256) void k_draws(const DevChain *__restrict__ dptr
     out[(long long)blockIdx.y * iters + i] = tdchain::draw_iteration(d.seed, d.chain, (uint64_t)(d.st->iter + i));
 }
 
-// A free-running launch outside tempering rounds: the recording instance when the launch records.
-template <bool SMALL, int NTH, bool RLDS>
-static void launch_free(bool rec, int grid, size_t lds, hipStream_t s, const DevChain *dev, int64_t iters,
-                        const ScriptArgs &sa) {
-    if (rec)
-        hipLaunchKernelGGL((k_chain_run<SMALL, false, NTH, RLDS, false, true>), dim3(grid), dim3(NTH), lds, s, dev,
-                           (long long)iters, sa);
-    else
-        hipLaunchKernelGGL((k_chain_run<SMALL, false, NTH, RLDS, false, false>), dim3(grid), dim3(NTH), lds, s, dev,
-                           (long long)iters, sa);
+hipError_t chain_query(const DevChain *dev, double x, double y, double z, const ScriptStep *edit, double *out,
+                       hipStream_t s) {
+    ScriptStep e{};
+    if (edit) e = *edit;
+    hipLaunchKernelGGL(k_chain_query, dim3(1), dim3(64), 0, s, dev, x, y, z, e, edit ? 1 : 0, out);
+    return hipGetLastError();
+}
+
+// The k_chain_run instances: what choose_chain_variant (chain_variant.h) can name, and nothing else.
+static_assert(kVariantThreads == kChainThreads, "chain_variant.h's thread count");
+using ChainKernel = void (*)(const DevChain *, long long, ScriptArgs);
+#define TD_CHAIN_INSTANCE(SMALL, SCRIPT, NTH, RLDS, ROUNDS, REC) \
+    {{SMALL, SCRIPT, NTH, RLDS, ROUNDS, REC}, k_chain_run<SMALL, SCRIPT, NTH, RLDS, ROUNDS, REC>}
+static const struct {
+    ChainVariant v;
+    ChainKernel k;
+} kChainInstances[] = {
+    // (the table's order is the instances' order of instantiation, so their order in the device module:
+    // treat a reordering like a change of k_chain_run's body, above)
+    // one 8-wave chain per CU, tiles, rays and order in LDS: free-running, scripted; the same, all in HBM
+    TD_CHAIN_INSTANCE(true, false, kChainThreads, true, false, false),
+    TD_CHAIN_INSTANCE(true, true, kChainThreads, true, false, false),
+    TD_CHAIN_INSTANCE(false, false, kChainThreads, false, false, false),
+    TD_CHAIN_INSTANCE(false, true, kChainThreads, false, false, false),
+    // two 4-wave chains per CU, free-running: all in HBM; the tiles in LDS
+    TD_CHAIN_INSTANCE(false, false, kChainThreads / 2, false, false, false),
+    TD_CHAIN_INSTANCE(true, false, kChainThreads / 2, false, false, false),
+    // exchange rounds (8 waves): LDS layout; all in HBM
+    TD_CHAIN_INSTANCE(true, false, kChainThreads, true, true, false),
+    TD_CHAIN_INSTANCE(false, false, kChainThreads, false, true, false),
+    // the four free-running ones, recording
+    TD_CHAIN_INSTANCE(true, false, kChainThreads, true, false, true),
+    TD_CHAIN_INSTANCE(false, false, kChainThreads, false, false, true),
+    TD_CHAIN_INSTANCE(false, false, kChainThreads / 2, false, false, true),
+    TD_CHAIN_INSTANCE(true, false, kChainThreads / 2, false, false, true),
+};
+#undef TD_CHAIN_INSTANCE
+
+int chain_variant_index(const ChainVariant &v) {
+    int i = 0;
+    for (const auto &e : kChainInstances) {
+        if (e.v == v) return i;
+        ++i;
+    }
+    return -1;
 }
 
 hipError_t chain_run(const DevChain *host, const DevChain *dev, int nchains, int64_t iters, hipStream_t s,
@@ -3256,82 +1955,24 @@ hipError_t chain_run(const DevChain *host, const DevChain *dev, int nchains, int
         sa.pin = pin_env;
         grid = 8;
     }
-    // one LDS size for the whole grid: the largest plan of any chain; the
-    // small (LDS-mirrored) variant only if every chain fits
-    size_t small = 0, big = 0, half = 0, hyb = 0;
-    // packed: every chain asks for two chains per CU (lds_mode 2: the tiles in LDS when they fit; 3, testing:
-    // the rays-in-HBM 4-wave kernel)
-    bool force_hbm = false, packed = true, tiles_ok = true, all_auto = true;
-    for (int b = 0; b < nchains; ++b) {
-        const DevChain &d = host[b];
-        small = std::max(small, lds_plan(d.ntiles, d.n, d.cap, true).total);
-        big = std::max(big, lds_plan(d.ntiles, d.n, d.cap, false).total);
-        half = std::max(half, lds_plan(d.ntiles, d.n, d.cap, false, kWaves / 2).total);
-        hyb = std::max(hyb, lds_plan(d.ntiles, d.n, d.cap, true, kWaves / 2, false).total);
-        force_hbm = force_hbm || d.lds_mode >= 1;
-        packed = packed && d.lds_mode >= 2;
-        tiles_ok = tiles_ok && d.lds_mode == 2;
-        all_auto = all_auto && d.lds_mode == 0;
-    }
-    const bool scripted = sa.n > 0 || sa.mb != nullptr;
-    bool rec = false;  // a recorded launch (td_chain_run_recorded): the instances that carry the sampling
-    for (int b = 0; b < nchains; ++b) rec = rec || host[b].rec.every > 0;
-    rec = rec && !scripted && sa.rb == nullptr && sa.rx == nullptr;
-    // More chains than CUs: one chain per CU would run them in rounds of num_cus workgroups; two
-    // 4-wave chains per CU run them all at once (1.35x the 8-wave kernel's rate at 512 config-3
-    // chains) -- the tiles-in-LDS kernel when it fits, else the all-in-HBM one
-    if (all_auto && num_cus > 0 && nchains > num_cus && !scripted && sa.rb == nullptr && sa.rx == nullptr &&
-        (hyb <= kLdsBudget / 2 || half <= kLdsBudget / 2)) {
-        packed = true;
-        tiles_ok = hyb <= kLdsBudget / 2;
-        force_hbm = true;
-    }
+    ChainLaunchFacts f = launch_facts(host, nchains);
+    f.scripted = sa.n > 0 || sa.mb != nullptr;
+    f.rx = sa.rx != nullptr;
+    f.rb = sa.rb != nullptr;
+    f.num_cus = num_cus;
+    const ChainChoice c = choose_chain_variant(f);
     static bool attr_set = false;  // dynamic LDS above 64 KB needs the attribute (once per kernel)
     if (!attr_set) {
-        for (const void *k : {(const void *)k_chain_run<true, false, kChainThreads>,
-                              (const void *)k_chain_run<true, true, kChainThreads>,
-                              (const void *)k_chain_run<false, false, kChainThreads>,
-                              (const void *)k_chain_run<false, true, kChainThreads>,
-                              (const void *)k_chain_run<false, false, kChainThreads / 2>,
-                              (const void *)k_chain_run<true, false, kChainThreads / 2, false>,
-                              (const void *)k_chain_run<true, false, kChainThreads, true, true>,
-                              (const void *)k_chain_run<false, false, kChainThreads, false, true>,
-                              (const void *)k_chain_run<true, false, kChainThreads, true, false, true>,
-                              (const void *)k_chain_run<false, false, kChainThreads, false, false, true>,
-                              (const void *)k_chain_run<false, false, kChainThreads / 2, false, false, true>,
-                              (const void *)k_chain_run<true, false, kChainThreads / 2, false, false, true>}) {
-            hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget);
-            if (e != hipSuccess) return e;
+        for (const auto &e : kChainInstances) {
+            hipError_t err = hipFuncSetAttribute((const void *)e.k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)kLdsBudget);
+            if (err != hipSuccess) return err;
         }
         attr_set = true;
     }
-    if (sa.rx != nullptr) {  // exchange rounds: one 8-wave chain per CU
-        if (small <= kLdsBudget && all_auto)
-            hipLaunchKernelGGL((k_chain_run<true, false, kChainThreads, true, true>), dim3(grid), dim3(kChainThreads),
-                               small, s, dev, (long long)iters, sa);
-        else
-            hipLaunchKernelGGL((k_chain_run<false, false, kChainThreads, false, true>), dim3(grid),
-                               dim3(kChainThreads), big, s, dev, (long long)iters, sa);
-    } else if (small <= kLdsBudget && !force_hbm) {
-        if (scripted)
-            hipLaunchKernelGGL((k_chain_run<true, true, kChainThreads>), dim3(grid), dim3(kChainThreads), small, s,
-                               dev, (long long)iters, sa);
-        else
-            launch_free<true, kChainThreads, true>(rec, grid, small, s, dev, iters, sa);
-    } else if (packed && !scripted && tiles_ok && hyb <= kLdsBudget / 2) {
-        // two chains resident per CU (4 waves, <= 80 KB of LDS each): the tiles in LDS, the rays and the
-        // order in HBM
-        launch_free<true, kChainThreads / 2, false>(rec, grid, hyb, s, dev, iters, sa);
-    } else if (packed && !scripted && half <= kLdsBudget / 2) {
-        // rays in HBM, 4 waves and <= 80 KB of LDS per chain: two chains resident per CU
-        launch_free<false, kChainThreads / 2, false>(rec, grid, half, s, dev, iters, sa);
-    } else {
-        if (scripted)
-            hipLaunchKernelGGL((k_chain_run<false, true, kChainThreads>), dim3(grid), dim3(kChainThreads), big, s,
-                               dev, (long long)iters, sa);
-        else
-            launch_free<false, kChainThreads, false>(rec, grid, big, s, dev, iters, sa);
-    }
+    const int at = chain_variant_index(c.v);
+    if (at < 0) return hipErrorInvalidValue;  // no such instance: never another kernel in its place
+    hipLaunchKernelGGL(kChainInstances[at].k, dim3(grid), dim3(c.v.nth), c.lds, s, dev, (long long)iters, sa);
     return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 """Child process of tests/test_gpu_skew_history.py: run with TD_LIB_PATH = the wave-skew build
-(mcmc-in-tonga_amd/libtdstar_skew.so, chain_kernels.hip SKEW).  Recorded runs of the device chain
+(mcmc-in-tonga_amd/libtdstar_skew.so, chain_diag.h SKEW).  Recorded runs of the device chain
 (td_chain_run_recorded: the sample copy and its barrier are skew sites too) against the HOST engine
 recording from its host loop, on the 8-cell model at max_cells 12 and the 200-cell one, every 1 and
 every 3: one JSON line per run -- the histories equal or not, the end states equal or not, and the skew

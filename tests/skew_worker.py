@@ -1,5 +1,5 @@
 """Child process of tests/test_gpu_skew.py: run with TD_LIB_PATH = the wave-skew build
-(mcmc-in-tonga_amd/libtdstar_skew.so, chain_kernels.hip SKEW).  The device chain against the host
+(mcmc-in-tonga_amd/libtdstar_skew.so, chain_diag.h SKEW).  The device chain against the host
 engine on test_gpu_chain's shapes (the 8-cell model at max_cells 12 first: inactive proposals every few
 iterations), printing one JSON line per launch: equal or not, and the skew build's spin-guard slot
 (nonzero: a spin wait gave up).  Stops at the first mismatch or guard trip (the state is then broken)."""

@@ -1,4 +1,4 @@
-"""The chain's phase-B tile filter (chain_kernels.hip tile_may_hit / tile_may_hit2, FP32) must never drop
+"""The chain's phase-B tile filter (chain_tiles.h tile_may_hit / tile_may_hit2, FP32) must never drop
 a tile that holds a point within the tile's cached maximum distance: in FP64, dist2(q, p) <= maxd for some
 point p of the tile => the tile passes.  Otherwise a proposal could miss a point whose nearest cell it
 changes (MCsub.jl:247-263 through the chain's incremental search).  Checked on tiles of 16 real ray points

@@ -1,4 +1,4 @@
-# The chain's wave-skew check (chain_kernels.hip SKEW, make skew-lib): the chain, bench-parity and
+# The chain's wave-skew check (chain_diag.h SKEW, make skew-lib): the chain, bench-parity and
 # drop-in tests on skew builds, each named on the command line as name=path.so.
 #   bash tools/gpu_skew.sh OUT name=ab/libtdstar_skew_new.so [name2=...]
 # A build's failures are recorded, not fatal (an old build may be expected to fail); a time limit is.

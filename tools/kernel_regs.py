@@ -22,9 +22,9 @@ for line in p.stderr.splitlines():
     if m and cur:
         rows[cur][m.group(1)] = int(m.group(2))
 for name, r in rows.items():
-    m = re.search(r"k_chain_runILb(\d)ELb(\d)ELi(\d+)ELb(\d)ELb(\d)E", name)
+    m = re.search(r"k_chain_runILb(\d)ELb(\d)ELi(\d+)ELb(\d)ELb(\d)ELb(\d)E", name)
     if not m:
         continue
-    print("k_chain_run<SMALL=%s SCRIPT=%s NTH=%s RLDS=%s ROUNDS=%s>: VGPR %d, VGPR spill %d, SGPR spill %d, scratch %d" % (
-        m.group(1), m.group(2), m.group(3), m.group(4), m.group(5), r.get("VGPRs", -1), r.get("VGPRs Spill", -1),
+    print("k_chain_run<SMALL=%s SCRIPT=%s NTH=%s RLDS=%s ROUNDS=%s REC=%s>: VGPR %d, VGPR spill %d, SGPR spill %d, scratch %d" % (
+        m.group(1), m.group(2), m.group(3), m.group(4), m.group(5), m.group(6), r.get("VGPRs", -1), r.get("VGPRs Spill", -1),
         r.get("SGPRs Spill", -1), r.get("ScratchSize [bytes/lane]", -1)))
