@@ -326,6 +326,50 @@ int td_history_rasterize(td_ctx *ctx, td_history *const *hs, int64_t nh, const d
                          const double *qz, int64_t nq, double *mean_out, double *std_out, double *values_out);
 
 /* ------------------------------------------------------------------------
+ * Posterior marginals -- what a trans-dimensional ensemble is read by beyond
+ * plot_model_hist's mean and std: per-node quantiles (median, credible
+ * interval), per-node histograms, and the ensemble distributions of
+ * plot_distribution.jl:66-80.  V[k][q] is td_rasterize's value matrix (model k
+ * at point q), M = nmodels; nothing but the results leaves the device.
+ *   quant_out[p*nq + q] = Statistics.quantile(V[:, q], probs[p]), Julia's
+ * default (alpha = beta = 1): with v = V[:, q] sorted ascending,
+ *     aleph = M*p + (1 - p);  j = clamp(trunc(aleph), 1, max(M-1, 1));
+ *     g = clamp(aleph - j, 0, 1);  a = v[j];  b = M == 1 ? v[1] : v[j+1]
+ *     quantile = a + g*(b - a)                      (1-based, unfused FP64)
+ * j and g are computed on the host; the device selects a and b exactly.  A
+ * column that holds a NaN gives NaN at every probability (Julia throws).
+ *   hist_out[q*(nbins+3) + s], with w = (hi - lo)/nbins (host, FP64), counts
+ * the models whose value at q falls in slot s:
+ *     0: v < lo;  1 + min((int)floor((v - lo)/w), nbins-1): lo <= v < hi;
+ *     nbins+1: v >= hi;  nbins+2: NaN            -- every row sums to M.
+ *   nprob 0..64 (0: no quantiles), nbins 0..4096 (0: no histogram); both 0
+ * returns mean and std only.  TD_ERR_ARG, before any HIP call: want NULL, a
+ * count out of range, a probability outside [0, 1] or NaN, lo/hi non-finite or
+ * lo >= hi with nbins > 0, a NULL array for a non-zero count.
+ *   mean_out / std_out are td_rasterize's, bit for bit.  Columns of up to
+ * 16384 models are sorted in LDS; longer ones take an exact radix select over
+ * the value matrix in device memory (csrc/marginals.hip); same results.
+ *   td_history_marginals is to td_rasterize_marginals what
+ * td_history_rasterize is to td_rasterize.
+ *   td_history_zeta_hist: the pooled histogram (same slots, nbins 1..4096) of
+ * every zeta of every sample the histories hold, counted where the samples
+ * lie, and, if ncells_out is non-NULL, each sample's number of cells, history
+ * by history (from the histories' host mirror of the offsets).
+ * ------------------------------------------------------------------------ */
+typedef struct td_marginals {
+    int64_t nprob; const double *probs; double *quant_out;   /* [nprob][nq]; nprob 0..64 */
+    int64_t nbins; double lo, hi;       int64_t *hist_out;   /* [nq][nbins+3]; nbins 0..4096 */
+} td_marginals;
+int td_rasterize_marginals(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const double *xCell,
+                           const double *yCell, const double *zCell, const double *zeta, const double *qx,
+                           const double *qy, const double *qz, int64_t nq, double *mean_out, double *std_out,
+                           const td_marginals *want);
+int td_history_marginals(td_ctx *ctx, td_history *const *hs, int64_t nh, const double *qx, const double *qy,
+                         const double *qz, int64_t nq, double *mean_out, double *std_out, const td_marginals *want);
+int td_history_zeta_hist(td_ctx *ctx, td_history *const *hs, int64_t nh, int64_t nbins, double lo, double hi,
+                         int64_t *hist_out /* nbins+3 */, int64_t *ncells_out /* one per sample, nullable */);
+
+/* ------------------------------------------------------------------------
  * Resident tempering rounds (parallel tempering; the reference's
  * chains are independent pmap workers, main_inversion.jl:15, so this is a new
  * capability): DEVICE chains of one context run in ONE launch that stays

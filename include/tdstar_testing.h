@@ -180,6 +180,15 @@ int tdt_shadow_profile(td_ctx *ctx, int64_t out[80]);
  * (distance, index) minimum). */
 int tdt_set_nn_method(td_ctx *ctx, int method);
 
+/* Posterior marginals (td_rasterize_marginals).  tdt_quantile_rank: the host's part of a quantile of M
+ * values at probability p, the 1-based j and the weight g of v[j+1] (include/tdstar.h); needs no GPU.
+ * tdt_set_marginals_method: the regime that selects the order statistics, 0 auto (resident up to
+ * tdt_marginals_resident_max models), 1 resident (columns sorted in LDS; a later call with more models
+ * than it holds returns TD_ERR_ARG), 2 streaming (radix select over device memory).  Same results. */
+int tdt_quantile_rank(int64_t M, double p, int64_t *j, double *g);
+int tdt_set_marginals_method(td_ctx *ctx, int method);
+int tdt_marginals_resident_max(td_ctx *ctx, int64_t *M);
+
 /* Diagnostic: the nearest-cell search alone, `reps` back-to-back launches over
  * the context's ray points on the given cells (method as tdt_set_nn_method,
  * 1..3), timed by two HIP events; *us_out = microseconds per search. */

@@ -46,6 +46,12 @@ class TdChainStats(ctypes.Structure):
                 ("phi", _d), ("ncells", _i64), ("bytes", _i64), ("last_action", _i32), ("last_accept", _i32)]
 
 
+class TdMarginals(ctypes.Structure):
+    """td_marginals; the arrays as plain addresses (ptr())."""
+    _fields_ = [("nprob", _i64), ("probs", _vp), ("quant_out", _vp), ("nbins", _i64), ("lo", _d), ("hi", _d),
+                ("hist_out", _vp)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/*.h
 SIGNATURES = {
     "td_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _pd, _pd, _pd, _pd, _pd, _i64, _i64, _pd, _pd]),
@@ -95,7 +101,15 @@ SIGNATURES = {
     "td_chain_run_batch_recorded": (ctypes.c_int, [ctypes.POINTER(_vp), _i64, _i64, _i64, _i64,
                                                    ctypes.POINTER(_vp)]),
     "td_history_rasterize": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, _pd, _pd, _pd, _i64, _pd, _pd, _pd]),
+    "td_rasterize_marginals": (ctypes.c_int, [_vp, _i64, _pi64, _pd, _pd, _pd, _pd, _pd, _pd, _pd, _i64, _pd, _pd,
+                                              ctypes.POINTER(TdMarginals)]),
+    "td_history_marginals": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, _pd, _pd, _pd, _i64, _pd, _pd,
+                                            ctypes.POINTER(TdMarginals)]),
+    "td_history_zeta_hist": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, _i64, _d, _d, _pi64, _pi64]),
     # include/tdstar_testing.h
+    "tdt_quantile_rank": (ctypes.c_int, [_i64, _d, _pi64, _pd]),
+    "tdt_set_marginals_method": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "tdt_marginals_resident_max": (ctypes.c_int, [_vp, _pi64]),
     "tdt_philox": (None, [_pu32, _pu32, _pu32]),
     "tdt_det_log": (_d, [_d]),
     "tdt_det_exp": (_d, [_d]),

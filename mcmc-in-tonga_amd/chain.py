@@ -176,6 +176,12 @@ class History:
                     phi=phi[:count], iter=it[:count], action=action[:count], accept=accept[:count],
                     ptS=None if ptS is None else ptS[:count])
 
+    def distributions(self, bins):
+        """The ensemble distributions of plot_distribution.jl:66-80 over this history's samples:
+        dict(zeta_hist[nbins + 3], ncells[samples]); ``bins`` = (nbins, lo, hi).  The zeta are counted
+        on the device (td_history_zeta_hist); posterior.model_distributions pools several histories."""
+        return self.ctx.zeta_hist([self], bins)
+
     def read(self, first=0, count=None, tS=None, likelihood=None):
         """The samples as ``Model`` copies, with what ``Chain.model()`` sets (nCells, cells, phi, ptS,
         action, accept) and, when given, the driver's tS / likelihood."""

@@ -60,6 +60,10 @@ struct td_ctx {
     int64_t raster_off_cap = 0;
     double *h_raster = nullptr;         // td_rasterize: pinned staging of queries and cells
     size_t h_raster_cap = 0;
+    void *marg = nullptr;               // marginals.hip workspace: rank parameters | quantiles | histogram counts
+    size_t marg_cap = 0;                // bytes
+    std::vector<unsigned char> marg_par_h;  // host copy of the rank parameters (the source of an async copy)
+    int marg_method = 0;                // quantile regime: 0 auto, 1 resident, 2 streaming (tdt_set_marginals_method)
     double cell_lo[3] = {0, 0, 0}, cell_hi[3] = {0, 0, 0};  // box of the uploaded cells (NaN skipped)
     int nn_method = 0;                  // 0 auto, 1 brute force, 2 bucket grid (tdt_set_nn_method)
     void *chain_desc = nullptr;         // device array of chain descriptors (td_chain_run_batch)

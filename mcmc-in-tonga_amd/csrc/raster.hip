@@ -20,6 +20,7 @@
 
 #include "ctx.h"
 #include "history.h"
+#include "marginals.h"
 
 namespace tdstar {
 
@@ -226,10 +227,12 @@ bool raster_batched(int64_t nmodels, int64_t total, int64_t nq) {
 // td_rasterize.  segs == nullptr: the cells are the host arrays.  Else (td_history_rasterize, the batched
 // launch only) they are in device memory already: histories' packed samples, segment after segment,
 // copied device to device behind the queries; cell_off is the concatenation's (host) prefix.
+// want (td_rasterize_marginals / td_history_marginals, else nullptr): quantiles and histograms of the
+// value matrix as well (marginals.hip), already checked by marg_check_want.
 int rasterize_core(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const double *xCell, const double *yCell,
                    const double *zCell, const double *zeta, const std::vector<td_history *> *segs, const double *qx,
                    const double *qy, const double *qz, int64_t nq, double *mean_out, double *std_out,
-                   double *values_out) {
+                   double *values_out, const td_marginals *want = nullptr) {
     if (!ctx) return set_err(nullptr, TD_ERR_ARG, "td_rasterize: ctx is NULL");
     if (nmodels < 1 || !cell_off || nq < 0 || (nq > 0 && (!qx || !qy || !qz || !mean_out || !std_out)))
         return set_err(ctx, TD_ERR_ARG, "td_rasterize: bad arguments");
@@ -345,6 +348,8 @@ int rasterize_core(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const 
     TD_HIP(ctx, hipGetLastError());
     TD_HIP(ctx, hipMemcpyAsync(mean_out, dm, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
     TD_HIP(ctx, hipMemcpyAsync(std_out, ds, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    if (want)
+        if (int rc = marginals_run(ctx, dv, nmodels, nq, want)) return rc;
     if (values_out)
         TD_HIP(ctx, hipMemcpyAsync(values_out, dv, sizeof(double) * (size_t)nq * nmodels, hipMemcpyDeviceToHost,
                                    ctx->stream));
@@ -362,9 +367,12 @@ extern "C" int td_rasterize(td_ctx *ctx, int64_t nmodels, const int64_t *cell_of
                           std_out, values_out);
 }
 
-extern "C" int td_history_rasterize(td_ctx *ctx, td_history *const *hs, int64_t nh, const double *qx,
-                                    const double *qy, const double *qz, int64_t nq, double *mean_out,
-                                    double *std_out, double *values_out) {
+namespace {
+
+// td_history_rasterize and td_history_marginals (want non-null)
+int history_rasterize(td_ctx *ctx, td_history *const *hs, int64_t nh, const double *qx, const double *qy,
+                      const double *qz, int64_t nq, double *mean_out, double *std_out, double *values_out,
+                      const td_marginals *want) {
     if (!ctx) return set_err(nullptr, TD_ERR_ARG, "td_history_rasterize: ctx is NULL");
     if (!hs || nh < 1) return set_err(ctx, TD_ERR_ARG, "td_history_rasterize: no history");
     std::vector<td_history *> segs;
@@ -381,7 +389,7 @@ extern "C" int td_history_rasterize(td_ctx *ctx, td_history *const *hs, int64_t 
     if (nmodels < 1) return set_err(ctx, TD_ERR_ARG, "td_history_rasterize: the histories hold no sample");
     if (raster_batched(nmodels, off.back(), nq))
         return rasterize_core(ctx, nmodels, off.data(), nullptr, nullptr, nullptr, nullptr, &segs, qx, qy, qz, nq,
-                              mean_out, std_out, values_out);
+                              mean_out, std_out, values_out, want);
     // the per-model search computes each model's bounding box on the host: fetch the cells
     const size_t total = (size_t)std::max<int64_t>(off.back(), 1);
     std::vector<double> c(4 * total);
@@ -395,5 +403,29 @@ extern "C" int td_history_rasterize(td_ctx *ctx, td_history *const *hs, int64_t 
         pos += (size_t)cnt;
     }
     return rasterize_core(ctx, nmodels, off.data(), c.data(), c.data() + total, c.data() + 2 * total,
-                          c.data() + 3 * total, nullptr, qx, qy, qz, nq, mean_out, std_out, values_out);
+                          c.data() + 3 * total, nullptr, qx, qy, qz, nq, mean_out, std_out, values_out, want);
+}
+
+}  // namespace
+
+extern "C" int td_history_rasterize(td_ctx *ctx, td_history *const *hs, int64_t nh, const double *qx,
+                                    const double *qy, const double *qz, int64_t nq, double *mean_out,
+                                    double *std_out, double *values_out) {
+    return history_rasterize(ctx, hs, nh, qx, qy, qz, nq, mean_out, std_out, values_out, nullptr);
+}
+
+extern "C" int td_rasterize_marginals(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const double *xCell,
+                                      const double *yCell, const double *zCell, const double *zeta, const double *qx,
+                                      const double *qy, const double *qz, int64_t nq, double *mean_out,
+                                      double *std_out, const td_marginals *want) {
+    if (int rc = marg_check_want(ctx, want, "td_rasterize_marginals")) return rc;
+    return rasterize_core(ctx, nmodels, cell_off, xCell, yCell, zCell, zeta, nullptr, qx, qy, qz, nq, mean_out,
+                          std_out, nullptr, want);
+}
+
+extern "C" int td_history_marginals(td_ctx *ctx, td_history *const *hs, int64_t nh, const double *qx,
+                                    const double *qy, const double *qz, int64_t nq, double *mean_out,
+                                    double *std_out, const td_marginals *want) {
+    if (int rc = marg_check_want(ctx, want, "td_history_marginals")) return rc;
+    return history_rasterize(ctx, hs, nh, qx, qy, qz, nq, mean_out, std_out, nullptr, want);
 }

@@ -157,6 +157,75 @@ class TdContext:
                                          ptr(std), ptr(vals) if want_values else None), self.h)
         return mean, std, vals
 
+    MARG_AUTO, MARG_RESIDENT, MARG_STREAMING = 0, 1, 2
+
+    def set_marginals_method(self, method):
+        """How ``marginals`` selects the order statistics: MARG_AUTO (columns sorted in LDS up to
+        ``marginals_resident_max()`` models, a radix select over device memory beyond), MARG_RESIDENT,
+        MARG_STREAMING.  Same answer."""
+        check(lib().tdt_set_marginals_method(self.h, int(method)), self.h)
+
+    def marginals_resident_max(self):
+        m = ctypes.c_int64()
+        check(lib().tdt_marginals_resident_max(self.h, ctypes.byref(m)), self.h)
+        return m.value
+
+    @staticmethod
+    def _marginals_want(nq, probs, bins):
+        """(td_marginals, the arrays it points to, quantiles or None, hist or None)"""
+        probs = f64(np.ravel(np.asarray(probs, dtype=np.float64)))
+        nbins, lo, hi = (int(bins[0]), float(bins[1]), float(bins[2])) if bins is not None else (0, 0.0, 0.0)
+        quant = np.empty((len(probs), nq)) if len(probs) else None
+        hist = np.zeros((nq, nbins + 3), dtype=np.int64) if nbins > 0 else None
+        want = _lib.TdMarginals(len(probs), ptr(probs) if len(probs) else None, ptr(quant), nbins, lo, hi,
+                                ptr(hist, _lib._pi64))
+        return want, (probs, quant, hist), quant, hist
+
+    def marginals(self, models, qx, qy, qz, probs=(), bins=None):
+        """td_rasterize_marginals: -> dict(mean[nq], std[nq], quantiles[nprob, nq] or None,
+        hist[nq, nbins + 3] or None).  ``probs``: probabilities in [0, 1] (Julia's default quantile
+        over the models at each point); ``bins`` = (nbins, lo, hi): per-point counts below lo, in the
+        nbins equal bins of [lo, hi), at or above hi, and NaN.  models as for ``rasterize``."""
+        off = np.zeros(len(models) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(m[0]) for m in models])
+        cx, cy, cz, cv = (f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) for k in range(4))
+        qx, qy, qz = (f64(np.ravel(a)) for a in (qx, qy, qz))
+        nq = len(qx)
+        mean, std = np.empty(nq), np.empty(nq)
+        want, held, quant, hist = self._marginals_want(nq, probs, bins)
+        check(lib().td_rasterize_marginals(self.h, len(models), ptr(off, _lib._pi64), ptr(cx), ptr(cy), ptr(cz),
+                                           ptr(cv), ptr(qx), ptr(qy), ptr(qz), nq, ptr(mean), ptr(std),
+                                           ctypes.byref(want)), self.h)
+        del held
+        return dict(mean=mean, std=std, quantiles=quant, hist=hist)
+
+    def marginals_history(self, histories, qx, qy, qz, probs=(), bins=None):
+        """td_history_marginals: ``marginals`` on the samples of the histories (chain.History), history by
+        history in sample order, without the models visiting the host."""
+        histories = list(histories)
+        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
+        qx, qy, qz = (f64(np.ravel(a)) for a in (qx, qy, qz))
+        nq = len(qx)
+        mean, std = np.empty(nq), np.empty(nq)
+        want, held, quant, hist = self._marginals_want(nq, probs, bins)
+        check(lib().td_history_marginals(self.h, hs, len(histories), ptr(qx), ptr(qy), ptr(qz), nq, ptr(mean),
+                                         ptr(std), ctypes.byref(want)), self.h)
+        del held
+        return dict(mean=mean, std=std, quantiles=quant, hist=hist)
+
+    def zeta_hist(self, histories, bins):
+        """td_history_zeta_hist: -> dict(zeta_hist[nbins + 3], ncells[samples]) over every sample of the
+        histories; ``bins`` = (nbins, lo, hi), slots as in ``marginals``."""
+        histories = list(histories)
+        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
+        nbins, lo, hi = int(bins[0]), float(bins[1]), float(bins[2])
+        hist = np.zeros(max(nbins, 0) + 3, dtype=np.int64)
+        nm = sum(len(h) for h in histories)
+        ncells = np.zeros(max(nm, 1), dtype=np.int64)
+        check(lib().td_history_zeta_hist(self.h, hs, len(histories), nbins, lo, hi, ptr(hist, _lib._pi64),
+                                         ptr(ncells, _lib._pi64)), self.h)
+        return dict(zeta_hist=hist, ncells=ncells[:nm])
+
     def interpolate(self, cells, X, Y, Z, want_nearest=False):
         """-> (zeta[npoints], nearest[npoints] or None)"""
         xc, yc, zc, ze = (f64(c) for c in cells)

@@ -23,10 +23,8 @@ def _flatten(model_hist):
     return out
 
 
-def section(ctx, models, xs, ys, zs, axis):
-    """One cross-section: axis "xz" (ys a scalar) or "xy" (zs a scalar); ``models``: Model objects, or
-    device histories (chain.History).
-    Returns (mean, std) as len(first) x len(second) matrices."""
+def _section_nodes(xs, ys, zs, axis):
+    """The nodes of a cross-section, xs fastest: (qx, qy, qz, (len(second), len(first)))."""
     if axis == "xz":
         a, b = np.asarray(xs, dtype=np.float64), np.asarray(zs, dtype=np.float64)
         qx, qz = np.tile(a, len(b)), np.repeat(b, len(a))
@@ -37,12 +35,38 @@ def section(ctx, models, xs, ys, zs, axis):
         qz = np.full(qx.shape, float(zs))
     else:
         raise ValueError(axis)
-    if models and all(hasattr(m, "read_arrays") for m in models):  # chain.History: rasterised where they lie
+    return qx, qy, qz, (len(b), len(a))
+
+
+def _on_device(models):
+    return bool(models) and all(hasattr(m, "read_arrays") for m in models)
+
+
+def section(ctx, models, xs, ys, zs, axis):
+    """One cross-section: axis "xz" (ys a scalar) or "xy" (zs a scalar); ``models``: Model objects, or
+    device histories (chain.History).
+    Returns (mean, std) as len(first) x len(second) matrices."""
+    qx, qy, qz, shape = _section_nodes(xs, ys, zs, axis)
+    if _on_device(models):  # chain.History: rasterised where they lie
         mean, std, _ = ctx.rasterize_history(models, qx, qy, qz)
     else:
         mean, std, _ = ctx.rasterize([m.cells() for m in models], qx, qy, qz)
-    shape = (len(b), len(a))  # column-major nx x n2 matrix, xs fastest
+    # shape: column-major nx x n2 matrix, xs fastest
     return mean.reshape(shape).T.copy(), std.reshape(shape).T.copy()
+
+
+def _sections(model_hist, dataStruct, TD_parameters):
+    """plot_model_hist's loop (MCsub.jl:756, :789): (the models, the grid vectors, [(axis, slice)])."""
+    if hasattr(model_hist, "read_arrays"):
+        model_hist = [model_hist]
+    models = _flatten(model_hist)
+    vecs = tuple(np.asarray(v, dtype=np.float64) for v in (dataStruct.xVec, dataStruct.yVec, dataStruct.zVec))
+    todo = []
+    if TD_parameters.xzMap:
+        todo += [("xz", l0) for l0 in TD_parameters.ySlice]
+    if TD_parameters.xyMap:
+        todo += [("xy", l0) for l0 in TD_parameters.zSlice]
+    return models, vecs, todo
 
 
 def plot_model_hist(model_hist, dataStruct, TD_parameters, cmax=None):  # noqa: N802 -- reference name
@@ -51,16 +75,8 @@ def plot_model_hist(model_hist, dataStruct, TD_parameters, cmax=None):  # noqa: 
     ``model_hist`` may also be a ``History`` or a list of them (one per chain): their samples, history
     by history, are the models, and stay on the device (td_history_rasterize)."""
     ctx = context_for(dataStruct)
-    if hasattr(model_hist, "read_arrays"):
-        model_hist = [model_hist]
-    models = _flatten(model_hist)
-    xv, yv, zv = (np.asarray(v, dtype=np.float64) for v in (dataStruct.xVec, dataStruct.yVec, dataStruct.zVec))
+    models, (xv, yv, zv), todo = _sections(model_hist, dataStruct, TD_parameters)
     maps = {}
-    todo = []
-    if TD_parameters.xzMap:
-        todo += [("xz", l0) for l0 in TD_parameters.ySlice]
-    if TD_parameters.xyMap:
-        todo += [("xy", l0) for l0 in TD_parameters.zSlice]
     for axis, l0 in todo:
         if axis == "xz":
             mean, std = section(ctx, models, xv, l0, zv, "xz")
@@ -69,3 +85,46 @@ def plot_model_hist(model_hist, dataStruct, TD_parameters, cmax=None):  # noqa: 
         mask = np.where(std > 5, np.nan, 1.0)
         maps[(axis, l0)] = {"mean": mean, "std": std, "masked": mask * mean}
     return maps
+
+
+def credible_maps(model_hist, dataStruct, TD_parameters, probs=(0.05, 0.5, 0.95), bins=None):
+    """Quantile maps of the ensemble over plot_model_hist's sections: the posterior of a
+    trans-dimensional run is a mixture over partitions, often bimodal at a boundary, which a mean and a
+    standard deviation do not describe.  Same inputs as ``plot_model_hist`` (Models, nested lists, a
+    ``History`` or a list of them); for each ("xz", y) / ("xy", z): ``quantiles`` [nprob, nx, n2]
+    (Julia's Statistics.quantile over the models at each node, m[i, j] orientation), ``width`` = the
+    last minus the first quantile, ``mean``, ``std`` and, with ``bins`` = (nbins, lo, hi), ``hist``
+    [nx, n2, nbins + 3] (below lo | nbins bins of [lo, hi) | at or above hi | NaN).  All computed on
+    the device (td_rasterize_marginals / td_history_marginals)."""
+    ctx = context_for(dataStruct)
+    models, (xv, yv, zv), todo = _sections(model_hist, dataStruct, TD_parameters)
+    maps = {}
+    for axis, l0 in todo:
+        if axis == "xz":
+            qx, qy, qz, shape = _section_nodes(xv, l0, zv, "xz")
+        else:
+            qx, qy, qz, shape = _section_nodes(xv, yv, l0, "xy")
+        if _on_device(models):
+            r = ctx.marginals_history(models, qx, qy, qz, probs, bins)
+        else:
+            r = ctx.marginals([m.cells() for m in models], qx, qy, qz, probs, bins)
+        out = {"mean": r["mean"].reshape(shape).T.copy(), "std": r["std"].reshape(shape).T.copy()}
+        q = r["quantiles"]
+        if q is not None:
+            out["quantiles"] = q.reshape((len(q),) + shape).transpose(0, 2, 1).copy()
+            out["width"] = out["quantiles"][-1] - out["quantiles"][0]
+        if r["hist"] is not None:
+            out["hist"] = r["hist"].reshape(shape + (r["hist"].shape[1],)).transpose(1, 0, 2).copy()
+        maps[(axis, l0)] = out
+    return maps
+
+
+def model_distributions(histories, bins):
+    """The ensemble distributions plot_distribution.jl:66-80 draws, of every sample of a ``History`` or a
+    list of them: ``zeta_hist`` [nbins + 3], the pooled histogram of all cells' zeta (``bins`` = (nbins,
+    lo, hi), slots as in ``credible_maps``) counted where the samples lie, and ``ncells``, each sample's
+    nCells, history by history."""
+    if hasattr(histories, "read_arrays"):
+        histories = [histories]
+    histories = list(histories)
+    return histories[0].ctx.zeta_hist(histories, bins)
