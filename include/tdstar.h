@@ -370,6 +370,71 @@ int td_history_zeta_hist(td_ctx *ctx, td_history *const *hs, int64_t nh, int64_t
                          int64_t *hist_out /* nbins+3 */, int64_t *ncells_out /* one per sample, nullable */);
 
 /* ------------------------------------------------------------------------
+ * Convergence diagnostics -- whether the chains an ensemble pools sample the
+ * same distribution (split Gelman-Rubin R-hat) and how many independent
+ * samples a node's statistics rest on (effective sample size, Geyer's initial
+ * monotone positive sequence), per column of a value matrix V[M][ncol]
+ * (model-major, td_rasterize's: model k at point q), where it lies.
+ *   Chains: nchains chains of lengths L_c >= 4, sum L_c = M; chain c is rows
+ * [P_c, P_c + L_c).  With N = min L_c and n = N / 2 (integer), every chain
+ * gives its LAST 2n rows as two sequences of n rows: sequence 2c is rows
+ * [P_c + L_c - 2n, P_c + L_c - n), sequence 2c+1 the n rows after it;
+ * m = 2 nchains.  T = n - 1 for max_lag 0, else min(n - 1, max_lag).
+ * tau_floor = 1 / log10((double)(m n)), computed on the host.
+ *   All FP64, IEEE, unfused; every sum starts at 0.0 and is sequential in the
+ * stated order.  Per column and sequence s with rows x_1..x_n:
+ *     mean_s = (x_1 + x_2 + ..., i ascending) / n;   d_i = x_i - mean_s
+ *     var_s  = (sum_i d_i d_i, i ascending) / (n - 1)
+ *     acov_s(t) = (sum_{i=1}^{n-t} d_i d_{i+t}, i ascending) / n      (t >= 1)
+ * per column:
+ *     W  = (sum_s var_s, s ascending) / m;     mu = (sum_s mean_s) / m
+ *     Bn = (sum_s (mean_s - mu)^2) / (m - 1)
+ *     vp = ((double)(n - 1) / (double)n) W + Bn
+ *     rhat = sqrt(vp / W)          (plain IEEE: 0/0 NaN, x/0 +inf)
+ *     A(t) = (sum_s acov_s(t), s ascending) / m;  rho(t) = 1 - (W - A(t)) / vp
+ *     Pprev = 1 + rho(1); S = Pprev; last = 1; capped = true
+ *     for k = 1, 2, ... while 2k + 1 <= T:
+ *         P = rho(2k) + rho(2k+1)
+ *         if not (P > 0): capped = false; break          (a NaN stops too)
+ *         if P > Pprev: P = Pprev
+ *         S = S + P; Pprev = P; last = 2k + 1
+ *     tau = -1 + 2 S; if tau < tau_floor: tau = tau_floor   (NaN stays NaN)
+ *     ess = (double)(m n) / tau
+ *     lags = capped ? -last : last
+ * A negative lags says that the cap or n ended the sum: tau is a lower bound.
+ * A constant column and a column that holds a NaN give NaN, NaN.
+ *   Each of rhat_out, ess_out, lags_out may be NULL; with ess_out and lags_out
+ * both NULL no autocovariance is computed.  TD_ERR_ARG, before any HIP call
+ * (the message, which names the entry point, through td_last_error(NULL)
+ * without a context): want NULL, max_lag < 0, the three outputs all NULL,
+ * nchains < 1, chain_len NULL, a length < 4, lengths that do not sum to M /
+ * nmodels, m n > INT32_MAX.
+ *   td_convergence_values: a host matrix (scalar traces such as phi or the
+ * number of cells), uploaded through the pinned staging block.
+ * td_rasterize_convergence: td_rasterize's models, the value matrix never
+ * leaving the device; mean_out / std_out are td_rasterize's, bit for bit.
+ * td_history_convergence is to it what td_history_rasterize is to
+ * td_rasterize: one history is one chain, a history without samples is
+ * skipped.  (csrc/convergence.hip; the lags are computed in rounds until
+ * every column has stopped, the results do not depend on the rounds.)
+ * ------------------------------------------------------------------------ */
+typedef struct td_convergence {
+    int64_t max_lag;                 /* >= 0; 0: up to n - 1 */
+    double *rhat_out, *ess_out;      /* [ncol], each nullable */
+    int32_t *lags_out;               /* [ncol], nullable */
+} td_convergence;
+int td_convergence_values(td_ctx *ctx, const double *values /* host [M][ncol] */, int64_t M, int64_t ncol,
+                          int64_t nchains, const int64_t *chain_len, const td_convergence *want);
+int td_rasterize_convergence(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const double *xCell,
+                             const double *yCell, const double *zCell, const double *zeta, const double *qx,
+                             const double *qy, const double *qz, int64_t nq, int64_t nchains,
+                             const int64_t *chain_len, double *mean_out, double *std_out,
+                             const td_convergence *want);
+int td_history_convergence(td_ctx *ctx, td_history *const *hs, int64_t nh, const double *qx, const double *qy,
+                           const double *qz, int64_t nq, double *mean_out, double *std_out,
+                           const td_convergence *want);
+
+/* ------------------------------------------------------------------------
  * Resident tempering rounds (parallel tempering; the reference's
  * chains are independent pmap workers, main_inversion.jl:15, so this is a new
  * capability): DEVICE chains of one context run in ONE launch that stays

@@ -189,6 +189,17 @@ int tdt_quantile_rank(int64_t M, double p, int64_t *j, double *g);
 int tdt_set_marginals_method(td_ctx *ctx, int method);
 int tdt_marginals_resident_max(td_ctx *ctx, int64_t *M);
 
+/* Convergence diagnostics (td_convergence_values).  tdt_convergence_plan: what the chain lengths and
+ * max_lag decide (include/tdstar.h), out = {n, m, T, first row of sequence 0}, seq_start [m] (nullable)
+ * every sequence's first row, *tau_floor (nullable); pure host code, TD_ERR_ARG as the entry points.
+ * tdt_set_convergence_round: the lags computed per round, 0 auto, else even and >= 2 (shrunk, not
+ * below 2, while the autocovariance scratch would exceed its budget).  tdt_set_convergence_lag_block:
+ * the lags one wave accumulates, 0 auto, 8 or 16.  Same results whatever either is. */
+int tdt_convergence_plan(int64_t nchains, const int64_t *chain_len, int64_t max_lag, int64_t out[4],
+                         int64_t *seq_start, double *tau_floor);
+int tdt_set_convergence_round(td_ctx *ctx, int64_t R);
+int tdt_set_convergence_lag_block(td_ctx *ctx, int LB);
+
 /* Diagnostic: the nearest-cell search alone, `reps` back-to-back launches over
  * the context's ray points on the given cells (method as tdt_set_nn_method,
  * 1..3), timed by two HIP events; *us_out = microseconds per search. */

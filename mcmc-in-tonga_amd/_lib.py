@@ -52,6 +52,11 @@ class TdMarginals(ctypes.Structure):
                 ("hist_out", _vp)]
 
 
+class TdConvergence(ctypes.Structure):
+    """td_convergence; the arrays as plain addresses (ptr())."""
+    _fields_ = [("max_lag", _i64), ("rhat_out", _vp), ("ess_out", _vp), ("lags_out", _vp)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/*.h
 SIGNATURES = {
     "td_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _pd, _pd, _pd, _pd, _pd, _i64, _i64, _pd, _pd]),
@@ -106,7 +111,15 @@ SIGNATURES = {
     "td_history_marginals": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, _pd, _pd, _pd, _i64, _pd, _pd,
                                             ctypes.POINTER(TdMarginals)]),
     "td_history_zeta_hist": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, _i64, _d, _d, _pi64, _pi64]),
+    "td_convergence_values": (ctypes.c_int, [_vp, _pd, _i64, _i64, _i64, _pi64, ctypes.POINTER(TdConvergence)]),
+    "td_rasterize_convergence": (ctypes.c_int, [_vp, _i64, _pi64, _pd, _pd, _pd, _pd, _pd, _pd, _pd, _i64, _i64, _pi64,
+                                                _pd, _pd, ctypes.POINTER(TdConvergence)]),
+    "td_history_convergence": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, _pd, _pd, _pd, _i64, _pd, _pd,
+                                              ctypes.POINTER(TdConvergence)]),
     # include/tdstar_testing.h
+    "tdt_convergence_plan": (ctypes.c_int, [_i64, _pi64, _i64, _pi64, _pi64, _pd]),
+    "tdt_set_convergence_round": (ctypes.c_int, [_vp, _i64]),
+    "tdt_set_convergence_lag_block": (ctypes.c_int, [_vp, ctypes.c_int]),
     "tdt_quantile_rank": (ctypes.c_int, [_i64, _d, _pi64, _pd]),
     "tdt_set_marginals_method": (ctypes.c_int, [_vp, ctypes.c_int]),
     "tdt_marginals_resident_max": (ctypes.c_int, [_vp, _pi64]),

@@ -176,6 +176,16 @@ class History:
                     phi=phi[:count], iter=it[:count], action=action[:count], accept=accept[:count],
                     ptS=None if ptS is None else ptS[:count])
 
+    def traces(self):
+        """The scalar traces of the samples, [samples, 2]: phi and nCells (the offsets' differences);
+        one td_history_read without the cells."""
+        count = self.count()[0]
+        off = np.zeros(count + 1, dtype=np.int64)
+        phi = np.zeros(max(count, 1))
+        check(lib().td_history_read(self.h, 0, count, ptr(off), None, None, None, None, 0, ptr(phi), None, None, None,
+                                    None), self.ctx.h)
+        return np.column_stack([phi[:count], np.diff(off).astype(np.float64)])
+
     def distributions(self, bins):
         """The ensemble distributions of plot_distribution.jl:66-80 over this history's samples:
         dict(zeta_hist[nbins + 3], ncells[samples]); ``bins`` = (nbins, lo, hi).  The zeta are counted

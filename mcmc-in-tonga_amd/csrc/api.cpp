@@ -306,11 +306,11 @@ void free_ctx(td_ctx *c) {
     void *dev[] = {c->g.px, c->g.py, c->g.pz, c->g.w, c->g.ray_off, c->g.tS, c->g.sig, c->g.terms, c->cells,
                    c->nn.part_d, c->nn.part_i, c->best_i, c->best_d, c->zeta0, c->phi,
                    c->q, c->q_i, c->q_z, c->chain_desc, c->draws, c->nn.g_count, c->nn.g_ent, c->raster, c->raster_i, c->raster_off,
-                   c->mf_dev, c->marg};
+                   c->mf_dev, c->marg, c->conv};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     void *host[] = {c->h_cells, c->h_out, c->h_best_i, c->h_q, c->h_q_i, c->h_q_z, c->h_chain_desc, c->mf_host,
-                    c->h_raster};
+                    c->h_raster, c->h_conv};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);

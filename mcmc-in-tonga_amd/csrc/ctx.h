@@ -64,6 +64,12 @@ struct td_ctx {
     size_t marg_cap = 0;                // bytes
     std::vector<unsigned char> marg_par_h;  // host copy of the rank parameters (the source of an async copy)
     int marg_method = 0;                // quantile regime: 0 auto, 1 resident, 2 streaming (tdt_set_marginals_method)
+    void *conv = nullptr;               // convergence.hip workspace: moments | round state | acov | sequence rows | flags
+    size_t conv_cap = 0;                // bytes
+    void *h_conv = nullptr;             // pinned: the count of active columns | the sequences' first rows
+    size_t h_conv_cap = 0;              // bytes
+    int64_t conv_round = 0;             // lags per round, 0 auto (tdt_set_convergence_round)
+    int conv_lb = 0;                    // lags per wave, 0 auto, 8 or 16 (tdt_set_convergence_lag_block)
     double cell_lo[3] = {0, 0, 0}, cell_hi[3] = {0, 0, 0};  // box of the uploaded cells (NaN skipped)
     int nn_method = 0;                  // 0 auto, 1 brute force, 2 bucket grid (tdt_set_nn_method)
     void *chain_desc = nullptr;         // device array of chain descriptors (td_chain_run_batch)

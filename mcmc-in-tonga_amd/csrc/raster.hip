@@ -18,6 +18,7 @@
 #include <cstring>
 #include <vector>
 
+#include "convergence.h"
 #include "ctx.h"
 #include "history.h"
 #include "marginals.h"
@@ -215,6 +216,24 @@ __global__ __launch_bounds__(256) void k_raster_stats(const double *__restrict__
 
 using namespace tdstar;
 
+int tdstar::raster_reserve(td_ctx *ctx, size_t nd, size_t nh) {
+    if (nd > ctx->raster_cap) {
+        if (ctx->raster) (void)hipFree(ctx->raster);
+        ctx->raster = nullptr;
+        ctx->raster_cap = 0;
+        TD_HIP(ctx, hipMalloc(&ctx->raster, sizeof(double) * nd));
+        ctx->raster_cap = nd;
+    }
+    if (nh > ctx->h_raster_cap) {
+        if (ctx->h_raster) (void)hipHostFree(ctx->h_raster);
+        ctx->h_raster = nullptr;
+        ctx->h_raster_cap = 0;
+        TD_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_raster), sizeof(double) * nh, hipHostMallocDefault));
+        ctx->h_raster_cap = nh;
+    }
+    return TD_OK;
+}
+
 namespace {
 
 // a section's few nodes: every model in one brute-force launch; many nodes: per model,
@@ -229,10 +248,12 @@ bool raster_batched(int64_t nmodels, int64_t total, int64_t nq) {
 // copied device to device behind the queries; cell_off is the concatenation's (host) prefix.
 // want (td_rasterize_marginals / td_history_marginals, else nullptr): quantiles and histograms of the
 // value matrix as well (marginals.hip), already checked by marg_check_want.
+// conv (td_rasterize_convergence / td_history_convergence, else nullptr): R-hat and ESS of the value
+// matrix's columns as well (convergence.hip), already checked by conv_check_want / conv_check_chains.
 int rasterize_core(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const double *xCell, const double *yCell,
                    const double *zCell, const double *zeta, const std::vector<td_history *> *segs, const double *qx,
                    const double *qy, const double *qz, int64_t nq, double *mean_out, double *std_out,
-                   double *values_out, const td_marginals *want = nullptr) {
+                   double *values_out, const td_marginals *want = nullptr, const ConvRequest *conv = nullptr) {
     if (!ctx) return set_err(nullptr, TD_ERR_ARG, "td_rasterize: ctx is NULL");
     if (nmodels < 1 || !cell_off || nq < 0 || (nq > 0 && (!qx || !qy || !qz || !mean_out || !std_out)))
         return set_err(ctx, TD_ERR_ARG, "td_rasterize: bad arguments");
@@ -247,26 +268,12 @@ int rasterize_core(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const 
     TD_HIP(ctx, hipSetDevice(ctx->device));
     // one device block: queries (3 nq), all cells SoA (4 total), values (nmodels nq), mean, std (2 nq)
     const size_t nd = 3 * (size_t)nq + 4 * (size_t)std::max<int64_t>(total, 1) + (size_t)nmodels * nq + 2 * (size_t)nq;
-    if (nd > ctx->raster_cap) {
-        if (ctx->raster) (void)hipFree(ctx->raster);
-        ctx->raster = nullptr;
-        ctx->raster_cap = 0;
-        TD_HIP(ctx, hipMalloc(&ctx->raster, sizeof(double) * nd));
-        ctx->raster_cap = nd;
-    }
-    double *dq = ctx->raster, *dc = dq + 3 * nq, *dv = dc + 4 * std::max<int64_t>(total, 1), *dm = dv + nmodels * nq,
-           *ds = dm + nq;
     const int64_t cs = std::max<int64_t>(total, 1);  // SoA stride of the cells
     // packed into a pinned staging block (reused across calls), then one DMA copy: pageable
     // copies of these sizes run at ~1 GB/s here
     const size_t nh = 3 * (size_t)nq + (segs ? 0 : 4 * (size_t)cs);
-    if (nh > ctx->h_raster_cap) {
-        if (ctx->h_raster) (void)hipHostFree(ctx->h_raster);
-        ctx->h_raster = nullptr;
-        ctx->h_raster_cap = 0;
-        TD_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_raster), sizeof(double) * nh, hipHostMallocDefault));
-        ctx->h_raster_cap = nh;
-    }
+    if (int rc = raster_reserve(ctx, nd, nh)) return rc;
+    double *dq = ctx->raster, *dc = dq + 3 * nq, *dv = dc + 4 * cs, *dm = dv + nmodels * nq, *ds = dm + nq;
     TD_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the staging block may still feed a previous copy
     double *h = ctx->h_raster;
     std::memcpy(h, qx, sizeof(double) * (size_t)nq);
@@ -350,6 +357,8 @@ int rasterize_core(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const 
     TD_HIP(ctx, hipMemcpyAsync(std_out, ds, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
     if (want)
         if (int rc = marginals_run(ctx, dv, nmodels, nq, want)) return rc;
+    if (conv)
+        if (int rc = convergence_run(ctx, dv, nmodels, nq, conv->nchains, conv->chain_len, conv->want)) return rc;
     if (values_out)
         TD_HIP(ctx, hipMemcpyAsync(values_out, dv, sizeof(double) * (size_t)nq * nmodels, hipMemcpyDeviceToHost,
                                    ctx->stream));
@@ -369,10 +378,11 @@ extern "C" int td_rasterize(td_ctx *ctx, int64_t nmodels, const int64_t *cell_of
 
 namespace {
 
-// td_history_rasterize and td_history_marginals (want non-null)
+// td_history_rasterize, td_history_marginals (want non-null) and td_history_convergence (cwant
+// non-null: one history with samples = one chain)
 int history_rasterize(td_ctx *ctx, td_history *const *hs, int64_t nh, const double *qx, const double *qy,
                       const double *qz, int64_t nq, double *mean_out, double *std_out, double *values_out,
-                      const td_marginals *want) {
+                      const td_marginals *want, const td_convergence *cwant = nullptr) {
     if (!ctx) return set_err(nullptr, TD_ERR_ARG, "td_history_rasterize: ctx is NULL");
     if (!hs || nh < 1) return set_err(ctx, TD_ERR_ARG, "td_history_rasterize: no history");
     std::vector<td_history *> segs;
@@ -387,9 +397,18 @@ int history_rasterize(td_ctx *ctx, td_history *const *hs, int64_t nh, const doub
     }
     const int64_t nmodels = (int64_t)off.size() - 1;
     if (nmodels < 1) return set_err(ctx, TD_ERR_ARG, "td_history_rasterize: the histories hold no sample");
+    std::vector<int64_t> lens;
+    ConvRequest creq{0, nullptr, cwant};
+    if (cwant) {
+        for (const td_history *h : segs) lens.push_back(h->samples);
+        creq.nchains = (int64_t)lens.size();
+        creq.chain_len = lens.data();
+        if (int rc = conv_check_chains(ctx, creq.nchains, creq.chain_len, nmodels, "td_history_convergence")) return rc;
+    }
+    const ConvRequest *conv = cwant ? &creq : nullptr;
     if (raster_batched(nmodels, off.back(), nq))
         return rasterize_core(ctx, nmodels, off.data(), nullptr, nullptr, nullptr, nullptr, &segs, qx, qy, qz, nq,
-                              mean_out, std_out, values_out, want);
+                              mean_out, std_out, values_out, want, conv);
     // the per-model search computes each model's bounding box on the host: fetch the cells
     const size_t total = (size_t)std::max<int64_t>(off.back(), 1);
     std::vector<double> c(4 * total);
@@ -403,7 +422,7 @@ int history_rasterize(td_ctx *ctx, td_history *const *hs, int64_t nh, const doub
         pos += (size_t)cnt;
     }
     return rasterize_core(ctx, nmodels, off.data(), c.data(), c.data() + total, c.data() + 2 * total,
-                          c.data() + 3 * total, nullptr, qx, qy, qz, nq, mean_out, std_out, values_out, want);
+                          c.data() + 3 * total, nullptr, qx, qy, qz, nq, mean_out, std_out, values_out, want, conv);
 }
 
 }  // namespace
@@ -428,4 +447,23 @@ extern "C" int td_history_marginals(td_ctx *ctx, td_history *const *hs, int64_t 
                                     double *std_out, const td_marginals *want) {
     if (int rc = marg_check_want(ctx, want, "td_history_marginals")) return rc;
     return history_rasterize(ctx, hs, nh, qx, qy, qz, nq, mean_out, std_out, nullptr, want);
+}
+
+extern "C" int td_rasterize_convergence(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const double *xCell,
+                                        const double *yCell, const double *zCell, const double *zeta, const double *qx,
+                                        const double *qy, const double *qz, int64_t nq, int64_t nchains,
+                                        const int64_t *chain_len, double *mean_out, double *std_out,
+                                        const td_convergence *want) {
+    if (int rc = conv_check_want(ctx, want, "td_rasterize_convergence")) return rc;
+    if (int rc = conv_check_chains(ctx, nchains, chain_len, nmodels, "td_rasterize_convergence")) return rc;
+    const ConvRequest conv{nchains, chain_len, want};
+    return rasterize_core(ctx, nmodels, cell_off, xCell, yCell, zCell, zeta, nullptr, qx, qy, qz, nq, mean_out,
+                          std_out, nullptr, nullptr, &conv);
+}
+
+extern "C" int td_history_convergence(td_ctx *ctx, td_history *const *hs, int64_t nh, const double *qx,
+                                      const double *qy, const double *qz, int64_t nq, double *mean_out,
+                                      double *std_out, const td_convergence *want) {
+    if (int rc = conv_check_want(ctx, want, "td_history_convergence")) return rc;
+    return history_rasterize(ctx, hs, nh, qx, qy, qz, nq, mean_out, std_out, nullptr, nullptr, want);
 }

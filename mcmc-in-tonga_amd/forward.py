@@ -226,6 +226,75 @@ class TdContext:
                                          ptr(ncells, _lib._pi64)), self.h)
         return dict(zeta_hist=hist, ncells=ncells[:nm])
 
+    CONV_ALL = ("rhat", "ess", "lags")
+
+    def set_convergence_round(self, R):
+        """The lags ``convergence`` computes per round (0: auto; else even, >= 2).  Same answer."""
+        check(lib().tdt_set_convergence_round(self.h, int(R)), self.h)
+
+    def set_convergence_lag_block(self, LB):
+        """The lags one wave of the autocovariance kernel accumulates (0: auto; 8; 16).  Same answer."""
+        check(lib().tdt_set_convergence_lag_block(self.h, int(LB)), self.h)
+
+    @staticmethod
+    def _convergence_want(ncol, max_lag, want):
+        """(td_convergence, dict of the arrays it points to)"""
+        out = {}
+        if "rhat" in want:
+            out["rhat"] = np.empty(ncol)
+        if "ess" in want:
+            out["ess"] = np.empty(ncol)
+        if "lags" in want:
+            out["lags"] = np.zeros(ncol, dtype=np.int32)
+        w = _lib.TdConvergence(int(max_lag), ptr(out.get("rhat")), ptr(out.get("ess")),
+                               ptr(out.get("lags"), _lib._pi32))
+        return w, out
+
+    def convergence(self, values, chain_len, max_lag=0, want=CONV_ALL):
+        """td_convergence_values: -> dict(rhat[ncol], ess[ncol], lags[ncol]) of the columns of
+        ``values`` [M, ncol] (or [M]: one column), whose rows are the chains' samples, chain after chain
+        with ``chain_len`` rows each.  Split R-hat over the halves of every chain's last 2n rows
+        (n = min(chain_len) // 2) and the effective sample size by Geyer's initial monotone sequence
+        over at most ``max_lag`` lags (0: n - 1); ``lags``: the last lag summed, negative where the cap
+        or n ended the sum (ess is then an upper bound).  ``want``: the subset to compute."""
+        V = f64(values)
+        if V.ndim == 1:
+            V = V.reshape(-1, 1)
+        lens = np.ascontiguousarray(chain_len, dtype=np.int64).ravel()
+        w, out = self._convergence_want(V.shape[1], max_lag, want)
+        check(lib().td_convergence_values(self.h, ptr(V), V.shape[0], V.shape[1], len(lens), ptr(lens, _lib._pi64),
+                                          ctypes.byref(w)), self.h)
+        return out
+
+    def convergence_models(self, models, chain_len, qx, qy, qz, max_lag=0, want=CONV_ALL):
+        """td_rasterize_convergence: ``convergence`` of the value matrix of ``rasterize`` (models as
+        there, chain after chain), which stays on the device; also ``mean`` and ``std``."""
+        off = np.zeros(len(models) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(m[0]) for m in models])
+        cat = [f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) for k in range(4)]
+        qx, qy, qz = (f64(np.ravel(a)) for a in (qx, qy, qz))
+        nq = len(qx)
+        lens = np.ascontiguousarray(chain_len, dtype=np.int64).ravel()
+        mean, std = np.empty(nq), np.empty(nq)
+        w, out = self._convergence_want(nq, max_lag, want)
+        check(lib().td_rasterize_convergence(self.h, len(models), ptr(off, _lib._pi64), *(ptr(c) for c in cat), ptr(qx),
+                                             ptr(qy), ptr(qz), nq, len(lens), ptr(lens, _lib._pi64), ptr(mean),
+                                             ptr(std), ctypes.byref(w)), self.h)
+        return dict(out, mean=mean, std=std)
+
+    def convergence_history(self, histories, qx, qy, qz, max_lag=0, want=CONV_ALL):
+        """td_history_convergence: ``convergence_models`` on the samples of the histories
+        (chain.History) where they lie: one history is one chain (one without samples is skipped)."""
+        histories = list(histories)
+        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
+        qx, qy, qz = (f64(np.ravel(a)) for a in (qx, qy, qz))
+        nq = len(qx)
+        mean, std = np.empty(nq), np.empty(nq)
+        w, out = self._convergence_want(nq, max_lag, want)
+        check(lib().td_history_convergence(self.h, hs, len(histories), ptr(qx), ptr(qy), ptr(qz), nq, ptr(mean),
+                                           ptr(std), ctypes.byref(w)), self.h)
+        return dict(out, mean=mean, std=std)
+
     def interpolate(self, cells, X, Y, Z, want_nearest=False):
         """-> (zeta[npoints], nearest[npoints] or None)"""
         xc, yc, zc, ze = (f64(c) for c in cells)

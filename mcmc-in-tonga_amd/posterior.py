@@ -128,3 +128,64 @@ def model_distributions(histories, bins):
         histories = [histories]
     histories = list(histories)
     return histories[0].ctx.zeta_hist(histories, bins)
+
+
+def _chains(model_hist):
+    """(the models or histories in order, the chain lengths): a nested model_hist[i][j] gives one chain per
+    inner list, a list of ``History`` one chain per history (one without samples is skipped), a flat
+    list of Models or a single ``History`` one chain."""
+    if hasattr(model_hist, "read_arrays"):
+        model_hist = [model_hist]
+    model_hist = list(model_hist)
+    if _on_device(model_hist):
+        return model_hist, [len(h) for h in model_hist if len(h) > 0]
+    if model_hist and all(isinstance(c, (list, tuple)) for c in model_hist):
+        return [m for c in model_hist for m in c], [len(c) for c in model_hist]
+    return model_hist, [len(model_hist)]
+
+
+def convergence_maps(model_hist, dataStruct, TD_parameters, max_lag=0):
+    """Whether the maps of ``plot_model_hist`` / ``credible_maps`` can be trusted: per node of the same
+    sections (m[i, j] orientation) ``rhat``, the split Gelman-Rubin statistic over the chains' halves,
+    ``ess``, the effective sample size (Geyer's initial monotone sequence over at most ``max_lag`` lags,
+    0: all), ``lags``, the last lag summed (negative: the cap or the chain length ended the sum, ess is an
+    upper bound), and ``mean``, ``std``; ``summary``: rhat_max (NaN ignored), ess_min, frac_rhat_above_1_01,
+    frac_capped, nan_columns, n (rows per half chain), m (half chains).  Chains: see ``_chains``; every chain
+    gives its last 2n samples, n = min length // 2.  All computed on the device (td_rasterize_convergence /
+    td_history_convergence)."""
+    ctx = context_for(dataStruct)
+    _, (xv, yv, zv), todo = _sections(model_hist, dataStruct, TD_parameters)
+    models, lens = _chains(model_hist)
+    maps = {}
+    for axis, l0 in todo:
+        if axis == "xz":
+            qx, qy, qz, shape = _section_nodes(xv, l0, zv, "xz")
+        else:
+            qx, qy, qz, shape = _section_nodes(xv, yv, l0, "xy")
+        if _on_device(models):
+            r = ctx.convergence_history(models, qx, qy, qz, max_lag)
+        else:
+            r = ctx.convergence_models([m.cells() for m in models], lens, qx, qy, qz, max_lag)
+        out = {f: r[f].reshape(shape).T.copy() for f in ("rhat", "ess", "lags", "mean", "std")}
+        rhat, ess = r["rhat"], r["ess"]
+        with np.errstate(invalid="ignore"):
+            out["summary"] = {
+                "rhat_max": float(np.nanmax(rhat)) if not np.all(np.isnan(rhat)) else float("nan"),
+                "ess_min": float(np.nanmin(ess)) if not np.all(np.isnan(ess)) else float("nan"),
+                "frac_rhat_above_1_01": float(np.mean(rhat > 1.01)),
+                "frac_capped": float(np.mean(r["lags"] < 0)),
+                "nan_columns": int(np.sum(np.isnan(rhat) | np.isnan(ess))),
+                "n": min(lens) // 2, "m": 2 * len(lens)}
+        maps[(axis, l0)] = out
+    return maps
+
+
+def trace_diagnostics(histories, max_lag=0):
+    """R-hat / ESS / lags of the two scalar traces of a ``History`` or a list of them (one chain each):
+    {"phi": {rhat, ess, lags}, "ncells": {...}}, through td_convergence_values with two columns."""
+    if hasattr(histories, "read_arrays"):
+        histories = [histories]
+    histories = [h for h in histories if len(h) > 0]
+    traces = [h.traces() for h in histories]
+    r = histories[0].ctx.convergence(np.concatenate(traces), [len(t) for t in traces], max_lag)
+    return {name: {f: r[f][k].item() for f in ("rhat", "ess", "lags")} for k, name in enumerate(("phi", "ncells"))}
