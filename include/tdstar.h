@@ -74,7 +74,8 @@ int td_get_info(const td_ctx *ctx, td_info *info);
 
 /* Per-kernel device timing with HIP events recorded on the context's stream
  * around every launch (off by default; used by bench.py for the roofline).
- * Kernel names: "nn_partial", "nn_merge", "ray_sums", "chi2", "chain_run".
+ * Kernel names: "nn_partial", "nn_merge", "ray_sums", "chi2", "chain_run",
+ * "history_pack" (a recorded ladder's slots packed, td_rounds_*_recorded).
  * td_timing_get waits for the recorded events and returns the launch count
  * and summed duration since the last reset. */
 int td_timing_enable(td_ctx *ctx, int enable);
@@ -310,8 +311,10 @@ int td_history_read(td_history *h, int64_t first, int64_t count, int64_t *off_ou
  * (hs[k] for chains[k]), in one launch -- the packed two-chains-per-CU kernels
  * included; a history listed twice is TD_ERR_ARG.
  *   A chain held by a running td_rounds launch is stopped first, as by every
- * other call.  Recording inside td_rounds_run / _temper / _exchange and in
- * td_evaluate's resident server is not provided. */
+ * other call.  A tempering ladder records the replica at ladder level 0 through
+ * td_rounds_temper_recorded / td_rounds_exchange_recorded (below, with the
+ * rounds); recording inside td_rounds_run, in a ladder spread over several
+ * ranks and in td_evaluate's resident server is not provided. */
 int td_chain_run_recorded(td_chain *ch, int64_t iterations, int64_t first, int64_t every, td_history *h);
 int td_chain_run_batch_recorded(td_chain *const *chains, int64_t nchains, int64_t iterations, int64_t first,
                                 int64_t every, td_history *const *hs);
@@ -474,6 +477,35 @@ int td_swap_decide(int64_t R, const double *phis, const int64_t *levels, const d
 int td_rounds_temper(td_rounds *r, int64_t M, int64_t K, const double *temps, int64_t *levels, int64_t rnd0,
                      uint64_t seed, double *phis_out, int64_t *levels_out, int64_t *tried, int64_t *accepted);
 
+/* td_rounds_temper, with the T = 1 ensemble of the ladder recorded in h: the
+ * sample of round j is the state of the replica that RAN the round at ladder
+ * level 0 (levels[k] == 0 when the round was posted -- the level, not a compare
+ * of temperatures), after the round's K-th proposal and before its swap step,
+ * laid out as td_chain_run_recorded's samples are (cells in Julia order, the
+ * chain's absolute iteration, the exact phi, ncells, action and accept of the
+ * round's last iteration, ptS when h keeps it).  Thinning counts ROUNDS: the
+ * call's rounds number first, first + every, ... (1-based; first >= 1, every
+ * >= 1) are sampled, and M rounds split over several calls with `first`
+ * carried over leave the history of one call.  Everything else -- every
+ * replica's trajectory, stats and end state, phis_out, levels, tried /
+ * accepted -- is td_rounds_temper's.
+ *   Temperatures move, not models, so the recorder is another workgroup from
+ * round to round: the kernel writes each sample into a slot of its own, and
+ * the call ends its resident launch before it packs the slots (one small
+ * kernel) and returns -- one relaunch per call, not per round.  On return h
+ * holds every sample of the call; td_history_count / _read and every
+ * td_history_* consumer work on it unchanged.
+ *   Capacity is checked on the host BEFORE anything runs, as for
+ * td_chain_run_recorded: with new = the samples the call takes and cells_each =
+ * the largest of the chains' max(max_cells, cells now), samples + new <=
+ * max_samples and cells_used + new * cells_each <= max_cells_total; otherwise
+ * TD_ERR_ARG with a message, and the ladder, the chains and h are unchanged.
+ * Also TD_ERR_ARG with a message: h NULL, h of another context, first < 1,
+ * every < 1. */
+int td_rounds_temper_recorded(td_rounds *r, int64_t M, int64_t K, const double *temps, int64_t *levels, int64_t rnd0,
+                              uint64_t seed, double *phis_out, int64_t *levels_out, int64_t *tried, int64_t *accepted,
+                              int64_t first, int64_t every, td_history *h);
+
 /* ------------------------------------------------------------------------
  * The exchange across GPUs (one replica per GPU, an RCCL allgather
  * over xGMI for the swap step).  A td_comm is an RCCL communicator of the
@@ -507,6 +539,17 @@ int td_comm_destroy(td_comm *c);
 int td_rounds_exchange(td_rounds *r, td_comm *comm, int64_t M, int64_t K, const double *temps, int64_t *levels,
                        int64_t rnd0, uint64_t seed, double *phis_out, int64_t *levels_out, int64_t *tried,
                        int64_t *accepted, double *timing_out);
+
+/* td_rounds_exchange with the ladder's T = 1 ensemble recorded in h, as
+ * td_rounds_temper_recorded records it (same samples, same checks): the
+ * workgroup that holds level 0 in a sampled round takes the sample itself.
+ * ONE rank only -- comm NULL, or a communicator of one rank; several ranks give
+ * TD_ERR_ARG with a message (the cold replica would wander between GPUs, which
+ * needs a merged history). */
+int td_rounds_exchange_recorded(td_rounds *r, td_comm *comm, int64_t M, int64_t K, const double *temps,
+                                int64_t *levels, int64_t rnd0, uint64_t seed, double *phis_out, int64_t *levels_out,
+                                int64_t *tried, int64_t *accepted, double *timing_out, int64_t first, int64_t every,
+                                td_history *h);
 
 #ifdef __cplusplus
 }

@@ -48,8 +48,21 @@ int tdt_chain_lds(td_chain *ch, int64_t out[4]);
  * tiles_ok, all_auto (over the chains' lds_mode); [8] scripted, [9] some chain records, [10] exchange
  * rounds, [11] resident tempering rounds; [12] nchains, [13] num_cus, [14] the LDS budget.
  * out: [0..5] SMALL, SCRIPT, NTH, RLDS, ROUNDS, REC; [6] LDS bytes; [7] the instance's index in the
- * launcher's table of 12, -1 if it has none (the launch would fail). */
+ * launcher's table, -1 if it has none (the launch would fail).  These 15 inputs reach positions 0..11. */
 int tdt_chain_variant(const int64_t in[15], int64_t out[8]);
+/* The same choice with the one fact tdt_chain_variant's inputs leave false: rounds_rec != 0 = the launch is a
+ * recorded ladder's (td_rounds_temper_recorded / td_rounds_exchange_recorded; it counts with in[10] or in[11]
+ * set).  Its instances sit at table positions >= 12. */
+int tdt_chain_variant_rounds(const int64_t in[15], int rounds_rec, int64_t out[8]);
+/* The pack kernel of a recorded ladder (csrc/history_pack.hip) on caller-given slots: cells = host [4][stride]
+ * (x, y, z, zeta rows), `count` slots of slot_cells cells from cell slot0 of every row, ncells[count] the cells
+ * each slot holds (0 .. slot_cells).  On return the samples lie packed from slot0 on in every row (the cells
+ * beyond them are unspecified) and off_out[0 .. count] are their offsets (off_out[0] = slot0).  The kernel
+ * moves tdt_history_pack_chunk() cells per round of its block.  TD_ERR_ARG before any HIP call for slots that
+ * do not fit the stride or a count outside its slot.  Needs a GPU. */
+int tdt_history_pack(int device, double *cells, int64_t stride, int64_t slot0, int64_t slot_cells,
+                     const int32_t *ncells, int64_t count, int64_t *off_out);
+int tdt_history_pack_chunk(void);
 /* Cycles of nq back-to-back nearest-cell queries through the chain's bucket grid by one wave
  * (pts: nq x {x, y, z}); mode 0: the whole query, 1: its loads only, 2: its arithmetic only.
  * out[0] = cycles, out[1] = unproven queries (full scans). */

@@ -74,6 +74,10 @@ SIGNATURES = {
                                         _pi64]),
     "td_rounds_exchange": (ctypes.c_int, [_vp, _vp, _i64, _i64, _pd, _pi64, _i64, ctypes.c_uint64, _pd, _pi64,
                                           _pi64, _pi64, _pd]),
+    "td_rounds_temper_recorded": (ctypes.c_int, [_vp, _i64, _i64, _pd, _pi64, _i64, ctypes.c_uint64, _pd, _pi64,
+                                                 _pi64, _pi64, _i64, _i64, _vp]),
+    "td_rounds_exchange_recorded": (ctypes.c_int, [_vp, _vp, _i64, _i64, _pd, _pi64, _i64, ctypes.c_uint64, _pd,
+                                                   _pi64, _pi64, _pi64, _pd, _i64, _i64, _vp]),
     "td_comm_unique_id": (ctypes.c_int, [ctypes.c_char_p]),
     "td_comm_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]),
     "td_comm_allgather": (ctypes.c_int, [_vp, _pd, _i64, _pd]),
@@ -132,6 +136,9 @@ SIGNATURES = {
     "tdt_chain_profile": (ctypes.c_int, [_vp, ctypes.c_int, _pi64]),
     "tdt_chain_lds": (ctypes.c_int, [_vp, _pi64]),
     "tdt_chain_variant": (ctypes.c_int, [_pi64, _pi64]),
+    "tdt_chain_variant_rounds": (ctypes.c_int, [_pi64, ctypes.c_int, _pi64]),
+    "tdt_history_pack": (ctypes.c_int, [ctypes.c_int, _pd, _i64, _i64, _i64, _pi32, _i64, _pi64]),
+    "tdt_history_pack_chunk": (ctypes.c_int, []),
     "tdt_chain_query_lat": (ctypes.c_int, [_vp, _pd, ctypes.c_int, ctypes.c_int, _pi64]),
     "tdt_chain_query_answers": (ctypes.c_int, [_vp, _pd, ctypes.c_int, ctypes.c_int, _pd, _pd, _pi32]),
     "tdt_tile_filter": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _pd,

@@ -820,6 +820,20 @@ int tdt_chain_variant(const int64_t in[15], int64_t out[8]) {
     return TD_OK;
 }
 
+int tdt_chain_variant_rounds(const int64_t in[15], int rounds_rec, int64_t out[8]) {
+    if (!in || !out) return TD_ERR_ARG;
+    ChainLaunchFacts f{(size_t)in[0], (size_t)in[1], (size_t)in[2], (size_t)in[3],  // (the struct's order)
+                       in[4] != 0,    in[5] != 0,    in[6] != 0,    in[7] != 0,
+                       in[8] != 0,    in[9] != 0,    in[10] != 0,   in[11] != 0,
+                       (int)in[12],   (int)in[13],   (size_t)in[14]};
+    f.rounds_rec = rounds_rec != 0;
+    const ChainChoice c = choose_chain_variant(f);
+    const int64_t o[8] = {c.v.small, c.v.script, c.v.nth, c.v.rlds, c.v.rounds, c.v.rec, (int64_t)c.lds,
+                          chain_variant_index(c.v)};
+    std::memcpy(out, o, sizeof(o));
+    return TD_OK;
+}
+
 int tdt_set_nn_method(td_ctx *ctx, int method) {
     if (!ctx || method < 0 || method > 3) return TD_ERR_ARG;
     ctx->nn_method = method == 3 ? 1 : method;  // 3: brute force through the split search

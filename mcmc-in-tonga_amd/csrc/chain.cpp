@@ -84,6 +84,9 @@ struct td_rounds {
     double tr_first = 0.0, tr_last = 0.0;  // diagnostic (TD_ROUNDS_TRACE): summed arrival times, rounds
     long long tr_n = 0;
     std::vector<char> force_exit;  // testing (tdt_rounds_force_exit): one-shot, per chain
+    // a recorded call (td_rounds_temper_recorded): per chain, the sample index the next posted round
+    // carries (RoundSlot::rec_i); empty outside such a call: every slot carries -1
+    std::vector<long long> rec_i;
     // exchange rounds (td_rounds_exchange, chain_dev.h RoundX): buffers made on first use
     int x_R = 0;                  // replicas the buffers are sized for
     double *x_in = nullptr, *x_out = nullptr, *x_temps = nullptr;  // device; x_in [2][local], x_out [2][R] by round parity
@@ -728,6 +731,12 @@ int rounds_stop(td_rounds *r) {
     return TD_OK;
 }
 
+// A ladder's recording (td_rounds_temper_recorded / td_rounds_exchange_recorded): the checks both make
+// before anything runs, and the descriptors' RecDesc for the call (defined with set_recording below).
+int rounds_recorded_check(td_rounds *r, const td_history *h, int64_t M, int64_t first, int64_t every, const char *who,
+                          int64_t *added, int64_t *cells_each);
+void rounds_set_recording(td_rounds *r, const td_history *h, int64_t first, int64_t every, int64_t cells_each);
+
 int rounds_start(td_rounds *r) {
     if (r->running) return TD_OK;
     td_ctx *c = r->ctx;
@@ -831,6 +840,7 @@ int td_rounds_run(td_rounds *r, int64_t K, const double *temps, double *phi_out)
             b->slot[k].T = ch->P.temperature;
             b->slot[k].inv_2t = ch->P.inv_2t;
             b->slot[k].skip = ran[(size_t)k];
+            b->slot[k].rec_i = r->rec_i.empty() ? -1 : r->rec_i[(size_t)k];
         }
         b->cmd = kRoundRun;
         b->K = (int)K;
@@ -930,10 +940,19 @@ int td_swap_decide(int64_t R, const double *phis, const int64_t *levels, const d
     return TD_OK;
 }
 
-int td_rounds_temper(td_rounds *r, int64_t M, int64_t K, const double *temps, int64_t *levels, int64_t rnd0,
-                     uint64_t seed, double *phis_out, int64_t *levels_out, int64_t *tried, int64_t *accepted) {
-    if (!r || M < 0 || K <= 0 || !temps || !levels || rnd0 < 0)
-        return set_err(r ? r->ctx : nullptr, TD_ERR_ARG, "td_rounds_temper");
+}  // extern "C"
+
+namespace {
+
+// td_rounds_temper, and with a history td_rounds_temper_recorded: the rounds' samples go into slots the
+// kernel picks by the index posted with each round (RoundSlot::rec_i: only the chain at level 0 gets
+// one); the launch is ended before the slots are packed and adopted -- a resident launch's device stores
+// are nothing the host may read while it runs, and the recorder's copy of the last round happens only
+// once its next command (here: QUIT) arrives.
+int rounds_temper(td_rounds *r, int64_t M, int64_t K, const double *temps, int64_t *levels, int64_t rnd0, uint64_t seed,
+                  double *phis_out, int64_t *levels_out, int64_t *tried, int64_t *accepted, int64_t first,
+                  int64_t every, td_history *h, const char *who) {
+    if (!r || M < 0 || K <= 0 || !temps || !levels || rnd0 < 0) return set_err(r ? r->ctx : nullptr, TD_ERR_ARG, who);
     const int64_t R = (int64_t)r->chains.size();
     std::vector<double> T((size_t)R), phi((size_t)R);
     std::vector<int64_t> nl((size_t)R);
@@ -941,21 +960,63 @@ int td_rounds_temper(td_rounds *r, int64_t M, int64_t K, const double *temps, in
         std::vector<char> seen((size_t)R, 0);
         for (int64_t k = 0; k < R; ++k) {
             if (levels[k] < 0 || levels[k] >= R || seen[(size_t)levels[k]])
-                return set_err(r->ctx, TD_ERR_ARG, "td_rounds_temper: levels are not a permutation");
+                return set_err(r->ctx, TD_ERR_ARG, std::string(who) + ": levels are not a permutation");
             seen[(size_t)levels[k]] = 1;
         }
     }
-    for (int64_t j = 0; j < M; ++j) {
-        for (int64_t k = 0; k < R; ++k) T[(size_t)k] = temps[levels[k]];
-        const int rc = td_rounds_run(r, K, T.data(), phi.data());
+    int64_t added = 0, cells_each = 0;
+    if (h) {  // (ends the running launch: the chains' cell counts are current; nothing else has run)
+        const int rc = rounds_recorded_check(r, h, M, first, every, who, &added, &cells_each);
         if (rc) return rc;
-        if (td_swap_decide(R, phi.data(), levels, temps, rnd0 + j, seed, nl.data(), tried, accepted))
-            return set_err(r->ctx, TD_ERR_ARG, "td_rounds_temper: levels are not a permutation");
+    }
+    const bool recording = h && added > 0;
+    if (recording) rounds_set_recording(r, h, first, every, cells_each);  // the next launch takes them
+    int rc = TD_OK;
+    for (int64_t j = 0; j < M && !rc; ++j) {
+        for (int64_t k = 0; k < R; ++k) T[(size_t)k] = temps[levels[k]];
+        if (recording) {  // round j + 1 of the call: sampled? by the chain at level 0
+            const int64_t n1 = j + 1;
+            const long long i = n1 >= first && (n1 - first) % every == 0 ? (long long)((n1 - first) / every) : -1;
+            r->rec_i.assign((size_t)R, -1);
+            for (int64_t k = 0; k < R; ++k)
+                if (levels[k] == 0) r->rec_i[(size_t)k] = i;
+        }
+        rc = td_rounds_run(r, K, T.data(), phi.data());
+        if (rc) break;
+        if (td_swap_decide(R, phi.data(), levels, temps, rnd0 + j, seed, nl.data(), tried, accepted)) {
+            rc = set_err(r->ctx, TD_ERR_ARG, std::string(who) + ": levels are not a permutation");
+            break;
+        }
         for (int64_t k = 0; k < R; ++k) levels[k] = nl[(size_t)k];
         if (phis_out) std::memcpy(phis_out + j * R, phi.data(), sizeof(double) * (size_t)R);
         if (levels_out) std::memcpy(levels_out + j * R, levels, sizeof(int64_t) * (size_t)R);
     }
-    return TD_OK;
+    if (!recording) return rc;
+    const int rs = rounds_stop(r);  // the last sampled round's copy is done when the launch has returned
+    r->rec_i.clear();
+    rounds_set_recording(r, nullptr, 0, 0, 0);
+    if (rc) return rc;
+    if (rs) return rs;
+    return history_pack_adopt(h, added, cells_each);
+}
+
+}  // namespace
+
+extern "C" {
+
+int td_rounds_temper(td_rounds *r, int64_t M, int64_t K, const double *temps, int64_t *levels, int64_t rnd0,
+                     uint64_t seed, double *phis_out, int64_t *levels_out, int64_t *tried, int64_t *accepted) {
+    return rounds_temper(r, M, K, temps, levels, rnd0, seed, phis_out, levels_out, tried, accepted, 1, 1, nullptr,
+                         "td_rounds_temper");
+}
+
+int td_rounds_temper_recorded(td_rounds *r, int64_t M, int64_t K, const double *temps, int64_t *levels, int64_t rnd0,
+                              uint64_t seed, double *phis_out, int64_t *levels_out, int64_t *tried, int64_t *accepted,
+                              int64_t first, int64_t every, td_history *h) {
+    if (!r) return set_err(nullptr, TD_ERR_ARG, "td_rounds_temper_recorded: NULL rounds");
+    if (!h) return set_err(r->ctx, TD_ERR_ARG, "td_rounds_temper_recorded: the history is NULL");
+    return rounds_temper(r, M, K, temps, levels, rnd0, seed, phis_out, levels_out, tried, accepted, first, every, h,
+                         "td_rounds_temper_recorded");
 }
 
 }  // extern "C"
@@ -1057,13 +1118,11 @@ T *dev_addr(T *host) {  // the device address of mapped pinned memory
     return hipHostGetDevicePointer(&d, host, 0) == hipSuccess ? static_cast<T *>(d) : nullptr;
 }
 
-}  // namespace
-
-extern "C" {
-
-int td_rounds_exchange(td_rounds *r, td_comm *comm, int64_t M, int64_t K, const double *temps, int64_t *levels,
-                       int64_t rnd0, uint64_t seed, double *phis_out, int64_t *levels_out, int64_t *tried,
-                       int64_t *accepted, double *timing_out) {
+// td_rounds_exchange, and with a history td_rounds_exchange_recorded (one rank): every workgroup knows the
+// levels and the round, so the one at level 0 takes the sample by itself (k_chain_run, ROUNDS && REC).
+int rounds_exchange(td_rounds *r, td_comm *comm, int64_t M, int64_t K, const double *temps, int64_t *levels,
+                    int64_t rnd0, uint64_t seed, double *phis_out, int64_t *levels_out, int64_t *tried,
+                    int64_t *accepted, double *timing_out, int64_t first, int64_t every, td_history *h) {
     if (!r || M < 0 || K <= 0 || K > INT32_MAX || M * K > ((int64_t)1 << 40) || !temps || !levels || rnd0 < 0)
         return set_err(r ? r->ctx : nullptr, TD_ERR_ARG, "td_rounds_exchange");
     td_ctx *c = r->ctx;
@@ -1090,6 +1149,12 @@ int td_rounds_exchange(td_rounds *r, td_comm *comm, int64_t M, int64_t K, const 
     servers_quiesce(nullptr);
     int rc = rounds_stop(r);  // this launch's host-posted rounds, whichever thread posted them
     if (rc) return rc;
+    int64_t added = 0, cells_each = 0;
+    if (h) {
+        rc = rounds_recorded_check(r, h, M, first, every, "td_rounds_exchange_recorded", &added, &cells_each);
+        if (rc) return rc;
+    }
+    const bool recording = h && added > 0;
     rc = exchange_alloc(r, (int)R, M);
     if (rc) return rc;
     if (comm) {  // entry barrier: every rank is here before any kernel's exchange watchdog starts
@@ -1099,6 +1164,7 @@ int td_rounds_exchange(td_rounds *r, td_comm *comm, int64_t M, int64_t K, const 
     // every chain starts at its level's temperature; the kernel's workgroups each keep all levels
     std::vector<int> lev0((size_t)local * (size_t)R);
     std::vector<int64_t> iter0((size_t)local);
+    if (recording) rounds_set_recording(r, h, first, every, cells_each);  // into this launch's descriptors only
     for (int k = 0; k < local; ++k) {
         iter0[(size_t)k] = r->chains[(size_t)k]->iter;
         td_chain *ch = r->chains[(size_t)k];
@@ -1110,6 +1176,7 @@ int td_rounds_exchange(td_rounds *r, td_comm *comm, int64_t M, int64_t K, const 
         ch->desc_dirty = true;  // (its own descriptor copy is refreshed on its next run)
         for (int64_t g = 0; g < R; ++g) lev0[(size_t)k * (size_t)R + (size_t)g] = (int)levels[g];
     }
+    if (recording) rounds_set_recording(r, nullptr, 0, 0, 0);  // (desc_host keeps the call's)
     *reinterpret_cast<volatile long long *>(r->x_err) = 0;
     TD_HIP(c, hipMemcpyAsync(r->x_lev, lev0.data(), sizeof(int) * lev0.size(), hipMemcpyHostToDevice, r->stream));
     TD_HIP(c, hipMemcpyAsync(r->x_temps, temps, sizeof(double) * (size_t)R, hipMemcpyHostToDevice, r->stream));
@@ -1233,6 +1300,10 @@ int td_rounds_exchange(td_rounds *r, td_comm *comm, int64_t M, int64_t K, const 
     }
     r->x_tag += (unsigned long long)M;
     r->x_gtag += (unsigned long long)M;
+    if (recording) {  // the launch has ended: the slots packed, the samples adopted
+        rc = history_pack_adopt(h, added, cells_each);
+        if (rc) return rc;
+    }
     if (timing_out) {
         // [0] the call, s; [1] launch issued, s; [2] exchanges enqueued, s; [3] mean time from this rank's phis
         // all in (workgroup 0 saw every local flag) to every phi gathered: the exchange; [4] mean time from
@@ -1256,6 +1327,35 @@ int td_rounds_exchange(td_rounds *r, td_comm *comm, int64_t M, int64_t K, const 
         timing_out[6] = (double)(t[3 * (M - 1) + 2] - t[0]) * tick;
     }
     return TD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int td_rounds_exchange(td_rounds *r, td_comm *comm, int64_t M, int64_t K, const double *temps, int64_t *levels,
+                       int64_t rnd0, uint64_t seed, double *phis_out, int64_t *levels_out, int64_t *tried,
+                       int64_t *accepted, double *timing_out) {
+    return rounds_exchange(r, comm, M, K, temps, levels, rnd0, seed, phis_out, levels_out, tried, accepted, timing_out,
+                           1, 1, nullptr);
+}
+
+int td_rounds_exchange_recorded(td_rounds *r, td_comm *comm, int64_t M, int64_t K, const double *temps,
+                                int64_t *levels, int64_t rnd0, uint64_t seed, double *phis_out, int64_t *levels_out,
+                                int64_t *tried, int64_t *accepted, double *timing_out, int64_t first, int64_t every,
+                                td_history *h) {
+    if (!r) return set_err(nullptr, TD_ERR_ARG, "td_rounds_exchange_recorded: NULL rounds");
+    if (!h) return set_err(r->ctx, TD_ERR_ARG, "td_rounds_exchange_recorded: the history is NULL");
+    if (comm && comm->nranks > 1)  // (the cold replica would wander between GPUs: a merged history)
+        return set_err(r->ctx, TD_ERR_ARG,
+                       "td_rounds_exchange_recorded: one rank only (comm NULL or of one rank), the communicator has " +
+                           std::to_string(comm->nranks));
+    if (first < 1 || every < 1)  // (before td_rounds_exchange's own checks and its M == 0 return)
+        return set_err(r->ctx, TD_ERR_ARG, "td_rounds_exchange_recorded: need first >= 1, every >= 1");
+    if (h->ctx != r->ctx)
+        return set_err(r->ctx, TD_ERR_ARG, "td_rounds_exchange_recorded: the history belongs to another context");
+    return rounds_exchange(r, comm, M, K, temps, levels, rnd0, seed, phis_out, levels_out, tried, accepted, timing_out,
+                           first, every, h);
 }
 
 int td_rounds_destroy(td_rounds *r) {
@@ -1449,6 +1549,42 @@ void set_recording(td_chain *ch, const td_history *h, int64_t first, int64_t eve
     }
     ch->dev.rec = r;
     ch->desc_dirty = true;
+}
+
+}  // namespace
+
+namespace {
+
+int rounds_recorded_check(td_rounds *r, const td_history *h, int64_t M, int64_t first, int64_t every, const char *who,
+                          int64_t *added, int64_t *cells_each) {
+    td_ctx *c = r->ctx;
+    if (!h) return set_err(c, TD_ERR_ARG, std::string(who) + ": the history is NULL");
+    if (h->ctx != c) return set_err(c, TD_ERR_ARG, std::string(who) + ": the history belongs to another context");
+    if (M < 0 || first < 1 || every < 1)
+        return set_err(c, TD_ERR_ARG, std::string(who) + ": need rounds >= 0, first >= 1, every >= 1");
+    const int rc = rounds_stop(r);  // (the chains' cell counts are the launch's until it returns)
+    if (rc) return rc;
+    *added = history_new_samples(M, first, every);
+    *cells_each = 0;
+    for (const td_chain *ch : r->chains) *cells_each = std::max(*cells_each, sample_cells_bound(ch));
+    return history_check_room(h, *added, *cells_each, who);
+}
+
+// h == nullptr: off again
+void rounds_set_recording(td_rounds *r, const td_history *h, int64_t first, int64_t every, int64_t cells_each) {
+    for (td_chain *ch : r->chains) {
+        RecDesc d{};
+        if (h) {
+            d = h->d;
+            d.cells = h->d.cells + h->off[(size_t)h->samples];  // the call's first slot
+            rec_set_slot(d, (long long)cells_each);
+            d.base = (long long)h->samples;
+            d.first = (long long)first;
+            d.every = (long long)every;
+        }
+        ch->dev.rec = d;
+        ch->desc_dirty = true;
+    }
 }
 
 }  // namespace

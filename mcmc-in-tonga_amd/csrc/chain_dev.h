@@ -87,10 +87,18 @@ constexpr int kMaxScript = 2;
 // prefix off[] of their offsets (off[base] is in place when the launch starts; sample k writes
 // off[k + 1]); a header per sample; ptS rows when the history keeps them.  The host has checked the
 // capacity for every sample of the launch: the kernel never tests for an overflow.
+//   A ladder's recording (td_rounds_temper_recorded / td_rounds_exchange_recorded; the ROUNDS && REC
+// instances): the recorder is another workgroup from round to round, so a sample's place depends on no
+// earlier sample -- sample i of the call (0-based) goes into the fixed slot cells + i * slot of each
+// component (cells = the history's first free cell, slot = the cells the capacity check reserved per
+// sample) with its header at base + i, and no off[] is read or written: history_pack.hip packs the
+// slots and forms the offsets after the launch.  first / every count ROUNDS of the call there.  The
+// slot size travels in the word of `off` (rec_slot / rec_set_slot below), which such a launch has no
+// other use for: the descriptor, and with it every instance's code that reads it, stays as it was.
 struct RecDesc {
     double *cells;     // [4][stride]: x, y, z, zeta
     long long stride;
-    long long *off;    // [max_samples + 1]
+    long long *off;    // [max_samples + 1]; a ladder's recording: the cells per slot, as an integer
     long long *iter;   // [max_samples] the absolute index of the iteration the sample follows
     double *phi;       // [max_samples] exact
     int *ncells, *action, *accept;  // [max_samples]
@@ -98,6 +106,9 @@ struct RecDesc {
     long long base;    // the index of the launch's first sample
     long long first, every;  // every == 0: recording off
 };
+
+__host__ __device__ inline long long rec_slot(const RecDesc &r) { return (long long)reinterpret_cast<intptr_t>(r.off); }
+inline void rec_set_slot(RecDesc &r, long long cells) { r.off = reinterpret_cast<long long *>((intptr_t)cells); }
 
 struct DevChain {
     // geometry (owned by the td_ctx)
@@ -218,7 +229,10 @@ struct RoundSlot {
     // (some other workgroup's watchdog fired as the round was posted): report phi again, run nothing
     long long skip;
     long long idle;  // testing (tdt_rounds_force_exit): > 0 = the idle watchdog of the launch's first wait, ticks
-    long long pad;
+    // host -> device, a recorded call (td_rounds_temper_recorded): the posted round's sample index in the
+    // call (RecDesc: slot and header) if this chain runs it at ladder level 0 and the round is sampled,
+    // else -1.  Read by the recording instances only, at the round's end, before phi is published.
+    long long rec_i;
 };
 struct RoundBox {
     long long seq;  // host -> device (written last)

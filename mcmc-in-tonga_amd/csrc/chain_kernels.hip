@@ -275,9 +275,59 @@ __device__ __attribute__((noinline)) void record_sample(const DevChain &d, const
     }
 }
 
+// One sample of a recorded ladder (RecDesc, chain_dev.h; the ROUNDS && REC instances), by the whole block
+// after the barrier that ends a round's last iteration: record_sample's copy into slot i of the call --
+// cells + i * slot, a place that is a function of the round alone, since the previous sample was another
+// workgroup's, whose stores this one has no way to see -- and the header at base + i.  No offset is read
+// or written (history_pack.hip).  A function of its own: record_sample and its callers stay as they are.
+__device__ __attribute__((noinline)) void record_round_sample(const DevChain &d, const int *ord, const double *ptS,
+                                                              const Shared &sh, long long i, long long iter,
+                                                              int action, int accept, int tid, int nth) {
+    const RecDesc &rc = d.rec;
+    const int nc = sh.ncells, n = d.n;
+    const long long k = rc.base + i;
+    double *ox = rc.cells + i * rec_slot(rc), *oy = ox + rc.stride, *oz = oy + rc.stride, *oze = oz + rc.stride;
+    const double *cx = d.cx, *cy = d.cy, *cz = d.cz, *cze = d.czeta;
+    constexpr int U = 4;
+    for (int j0 = tid; j0 < nc; j0 += U * nth) {
+        int s[U];
+        double x[U], y[U], z[U], ze[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) s[u] = ord[min(j0 + u * nth, nc - 1)];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            x[u] = gload(cx + s[u]);
+            y[u] = gload(cy + s[u]);
+            z[u] = gload(cz + s[u]);
+            ze[u] = gload(cze + s[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * nth;
+            if (j < nc) {
+                gstore(ox + j, x[u]);
+                gstore(oy + j, y[u]);
+                gstore(oz + j, z[u]);
+                gstore(oze + j, ze[u]);
+            }
+        }
+    }
+    if (rc.ptS) {
+        double *op = rc.ptS + k * n;
+        for (int r = tid; r < n; r += nth) gstore(op + r, ptS[r]);
+    }
+    if (tid == 0) {
+        rc.iter[k] = iter;
+        rc.phi[k] = sh.phi;
+        rc.ncells[k] = nc;
+        rc.action[k] = action;
+        rc.accept[k] = accept;
+    }
+}
+
 // ---------------------------------------------------------------- k_chain_run ----
 // The body below is one function on purpose, and is changed only with a comparison of the generated
-// assembly of all 12 instances and a same-machine A/B: every instance sits at 256 VGPRs with 976-1280 B
+// assembly of all 14 instances and a same-machine A/B: every instance sits at 256 VGPRs with 976-1280 B
 // per lane of scratch, and its register allocation moves with any restructuring -- wrapping only the
 // mirror preamble in an always-inlined lambda changed the allocation of every LDS-layout instance
 // (scratch +16 B/lane in two, spill counts up in three and down in two).  So no phase is extracted and
@@ -287,7 +337,9 @@ __device__ __attribute__((noinline)) void record_sample(const DevChain &d, const
 // that code on its path.
 // SMALL: the tiles mirrored in LDS (else in HBM, with super-tiles); RLDS: the per-ray arrays and the
 // Julia order mirrored too (the 381-ray configs, 8 waves); NTH: 512 threads, or 256 (two chains per CU)
-// REC: a recorded launch (RecDesc): the instances without it carry none of its code
+// REC: a recorded launch (RecDesc): the instances without it carry none of its code.  With ROUNDS: a
+// ladder's recording (either round protocol: sa.rb or sa.rx), the sample of a round taken by the workgroup
+// that ran it at ladder level 0 (record_round_sample); without: a free-running chain's (record_sample)
 template <bool SMALL, bool SCRIPT, int NTH, bool RLDS = SMALL, bool ROUNDS = false, bool REC = false>
 __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict__ dptr, long long iters,
                                                              ScriptArgs sa) {
@@ -295,7 +347,7 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
     constexpr bool kNoBarB = RLDS && !SCRIPT;     // phase B may end without a block barrier (below)
     constexpr int kWv = NTH / 64;  // waves: 8 (one chain per CU), or 4 (rays in HBM: two chains per CU)
     static_assert(!RLDS || SMALL, "rays in LDS only with the tiles in LDS");
-    static_assert(!REC || (!SCRIPT && !ROUNDS), "recording: free-running chains outside tempering rounds");
+    static_assert(!REC || !SCRIPT, "recording: drawn proposals (free-running chains, tempering rounds)");
     static_assert(NTH == kChainThreads || (!RLDS && !SCRIPT && NTH == kChainThreads / 2),
                   "512 threads, or 256 with the rays in HBM");
     if (sa.pin >= 0) {  // one chain, launched as 8 workgroups: only the one on XCD `pin` runs it
@@ -543,8 +595,13 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
     long long it_done = 0;                 // iterations run (server mode: until QUIT)
     // recording (RecDesc): the launch's next sampled iteration, 1-based (block-uniform; never, when off)
     long long rec_next = LLONG_MAX;
-    if constexpr (REC)
+    if constexpr (REC && !ROUNDS)
         if (d.rec.every > 0 && !rbx) rec_next = d.rec.first;
+    // a ladder's recording: wave 0 latches a round's sample index in sh.mbox[0] (-1: none) and the round's
+    // last iteration, 1-based, in sh.mbox[1] (server words, idle in these instances) before the round's
+    // barrier; the block reads them after it
+    if constexpr (REC && ROUNDS)
+        if (tid == 0) sh.mbox[0] = sh.mbox[1] = -1;
     // LDS layout, decisions on bounds (phase F): a proposal accepted on bounds of phi_n leaves its
     // chi^2 partial sums unformed -- prefix[] stays exact below ex_upto only (wave 0), and tid 0
     // keeps phi_r as an estimate inside [phi_lo, phi_hi].  They are made exact again by the next
@@ -1668,7 +1725,7 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
         // ===== end of iteration: the next proposal (wave 0; draws refilled every 64) =====
         if (wv == 0) {
             if (prof_on && lane == 0) sh.prof[7 + action] += clock64() - sh.t_iter;  // per-action totals
-            if constexpr (REC) {
+            if constexpr (REC && !ROUNDS) {
                 if (it + 1 == rec_next) {  // a sample's phi is exact (phase F made the sums so, unless nothing was evaluated)
                     phi_r = exact_sums(v.term, v.prefix, v.cprefix, v.cterm, v.rflag, sh, n, lane, false, n, phi_r, 0.0).phi;
                     if (lane == 0) sh.phi = phi_r;  // read by record_sample after the iteration-end barrier
@@ -1678,6 +1735,28 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
                 {  // (a phase F of this iteration made every sum exact already)
                     phi_r = exact_sums(v.term, v.prefix, v.cprefix, v.cterm, v.rflag, sh, n, lane, false, n, phi_r, 0.0).phi;
                     if (lane == 0) sh.phi = phi_r;
+                }
+                if constexpr (REC && ROUNDS) {
+                    // Does this workgroup record the round?  Latched here, before round_wait /
+                    // round_exchange publish phi and take the next round's level: host-decided rounds
+                    // carry the answer in the slot (still the posted round's words: the host rewrites
+                    // them only once it has seen `done`); exchange rounds have the levels of the round
+                    // in x.lev (each lane reads the word it wrote itself) and the round's number
+                    long long ri = -1;
+                    if (rbx) {
+                        if (lane == 0) ri = mb_load(&rbx->slot[bchain].rec_i);
+                    } else if (d.rec.every > 0) {
+                        const RoundX &x = *rxp;
+                        const int lv = lane < x.R ? x.lev[bchain * x.R + lane] : -1;
+                        const int mine = __shfl(lv, (x.rank * x.local + bchain) & 63);
+                        const long long jr = (it + 1) / x.K;  // the call's round, 1-based
+                        if (mine == 0 && jr >= d.rec.first && (jr - d.rec.first) % d.rec.every == 0)
+                            ri = (jr - d.rec.first) / d.rec.every;
+                    }
+                    if (lane == 0) {
+                        sh.mbox[0] = d.rec.every > 0 ? ri : -1;
+                        sh.mbox[1] = it + 1;
+                    }
                 }
                 if (rbx) {
                     round_wait(rbx, bchain, sh, lane, true, phi_r);  // (lane 0 = tid 0 holds phi)
@@ -1748,7 +1827,16 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
         __syncthreads();
         STAMP(6);
         SKEW(17);
-        if constexpr (REC) {
+        if constexpr (REC && ROUNDS) {
+            // a round this workgroup ran at level 0 (wave 0's latch, above this barrier; block-uniform):
+            // its model into the round's slot.  The next latch is at least one iteration's barriers away.
+            if (sh.mbox[1] == it + 1 && sh.mbox[0] >= 0) {
+                record_round_sample(d, v.ord, v.ptS, sh, sh.mbox[0], iter0 + it, last_action, last_accept, tid, NTH);
+                __syncthreads();  // the copy is done before a later phase G changes the cells, the order or ptS
+                SKEW(20);
+            }
+        }
+        if constexpr (REC && !ROUNDS) {
             if (it + 1 == rec_next) {  // this iteration's model into the history (block-uniform)
                 record_sample(d, v.ord, v.ptS, sh, it, iter0, last_action, last_accept, tid, NTH);
                 rec_next += d.rec.every;
@@ -1903,6 +1991,9 @@ static const struct {
     TD_CHAIN_INSTANCE(false, false, kChainThreads, false, false, true),
     TD_CHAIN_INSTANCE(false, false, kChainThreads / 2, false, false, true),
     TD_CHAIN_INSTANCE(true, false, kChainThreads / 2, false, false, true),
+    // a ladder's recording (host-decided rounds and exchange rounds alike): LDS layout; all in HBM
+    TD_CHAIN_INSTANCE(true, false, kChainThreads, true, true, true),
+    TD_CHAIN_INSTANCE(false, false, kChainThreads, false, true, true),
 };
 #undef TD_CHAIN_INSTANCE
 
@@ -1959,6 +2050,7 @@ hipError_t chain_run(const DevChain *host, const DevChain *dev, int nchains, int
     f.scripted = sa.n > 0 || sa.mb != nullptr;
     f.rx = sa.rx != nullptr;
     f.rb = sa.rb != nullptr;
+    f.rounds_rec = f.rec && (f.rx || f.rb);  // set by td_rounds_temper_recorded / td_rounds_exchange_recorded alone
     f.num_cus = num_cus;
     const ChainChoice c = choose_chain_variant(f);
     static bool attr_set = false;  // dynamic LDS above 64 KB needs the attribute (once per kernel)

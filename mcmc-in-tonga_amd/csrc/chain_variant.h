@@ -3,7 +3,8 @@
 // chain_run (chain_kernels.hip) folds its chains' LDS plans and lds_modes into the facts below, asks
 // choose_chain_variant() and launches the table entry it names; chain_lds_sizes (chain_state.hip)
 // asks it for one free-running chain; tests/test_chain_variant.py holds it, through
-// tdt_chain_variant, against the if-chain it replaced.
+// tdt_chain_variant, against the if-chain it replaced, and tests/test_chain_variant_rounds.py, through
+// tdt_chain_variant_rounds, holds what a ladder's recording adds.
 #pragma once
 
 #include <cstddef>
@@ -35,6 +36,10 @@ struct ChainLaunchFacts {
     bool rx, rb;    // exchange rounds; resident tempering rounds
     int nchains, num_cus;
     size_t budget;  // kLdsBudget
+    // a ladder's recording (td_rounds_temper_recorded / td_rounds_exchange_recorded; with rb or rx): the
+    // launch samples the replica at ladder level 0.  Last, and absent from tdt_chain_variant's 15 inputs:
+    // `rec` with rb or rx alone still names a non-recording instance.
+    bool rounds_rec;
 };
 
 struct ChainChoice {
@@ -54,6 +59,10 @@ inline ChainChoice choose_chain_variant(ChainLaunchFacts f) {
         f.packed = true;
         f.tiles_ok = f.hyb <= f.budget / 2;
         f.force_hbm = true;
+    }
+    if (f.rounds_rec && (f.rx || f.rb)) {  // a recorded ladder, either round protocol: one 8-wave chain per CU
+        if (f.small <= f.budget && f.all_auto) return {{true, false, T, true, true, true}, f.small};
+        return {{false, false, T, false, true, true}, f.big};
     }
     if (f.rx) {  // exchange rounds: one 8-wave chain per CU
         if (f.small <= f.budget && f.all_auto) return {{true, false, T, true, true, false}, f.small};

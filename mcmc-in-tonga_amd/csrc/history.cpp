@@ -3,6 +3,8 @@
 // by k_chain_run itself (chain_kernels.hip record_sample).
 #include "history.h"
 
+#include "../../include/tdstar_testing.h"
+
 #include <algorithm>
 #include <new>
 #include <string>
@@ -45,6 +47,20 @@ int history_adopt(td_history *h, int64_t added) {
                              sizeof(int64_t) * (size_t)added, hipMemcpyDeviceToHost));
     h->samples += added;
     return TD_OK;
+}
+
+int history_pack_adopt(td_history *h, int64_t added, int64_t cells_each) {
+    if (added <= 0) return TD_OK;
+    td_ctx *c = h->ctx;
+    const int64_t base = h->samples, used = h->off[(size_t)base];
+    Timer *tm = c->timer.on ? &c->timer : nullptr;
+    hipEvent_t t0 = tm ? tm->begin(c->stream) : nullptr;
+    const hipError_t e = launch_history_pack(h->d.cells, h->d.stride, (long long)used, (long long)cells_each,
+                                             h->d.ncells + base, (long long)added, h->d.off + base, c->stream);
+    if (tm) tm->end("history_pack", t0, c->stream);
+    if (e != hipSuccess) return hip_err(c, e, "k_history_pack launch");
+    TD_HIP(c, hipStreamSynchronize(c->stream));
+    return history_adopt(h, added);
 }
 
 int history_append_host(td_history *h, const double *x, const double *y, const double *z, const double *zeta,
@@ -176,6 +192,49 @@ int td_history_read(td_history *h, int64_t first, int64_t count, int64_t *off_ou
     if (ptS_out && h->d.ptS)
         TD_HIP(c, hipMemcpy(ptS_out, h->d.ptS + first * h->n, sizeof(double) * cnt * (size_t)h->n,
                             hipMemcpyDeviceToHost));
+    return TD_OK;
+}
+
+int tdt_history_pack_chunk(void) { return kPackChunk; }
+
+int tdt_history_pack(int device, double *cells, int64_t stride, int64_t slot0, int64_t slot_cells,
+                     const int32_t *ncells, int64_t count, int64_t *off_out) {
+    // (every check before any HIP call: the kernel tests no bound)
+    if (!cells || !ncells || !off_out || stride < 1 || slot0 < 0 || slot_cells < 0 || count < 0 ||
+        stride > ((int64_t)1 << 32) || count > ((int64_t)1 << 32))
+        return set_err(nullptr, TD_ERR_ARG, "tdt_history_pack: bad arguments");
+    if (count > 0 && slot_cells > (stride - slot0) / count)
+        return set_err(nullptr, TD_ERR_ARG, "tdt_history_pack: the slots do not fit the stride");
+    for (int64_t i = 0; i < count; ++i)
+        if (ncells[i] < 0 || ncells[i] > slot_cells)
+            return set_err(nullptr, TD_ERR_ARG, "tdt_history_pack: a sample larger than its slot");
+    off_out[0] = slot0;
+    if (count == 0) return TD_OK;
+    if (device >= 0) TD_HIP(nullptr, hipSetDevice(device));
+    const size_t cb = sizeof(double) * 4 * (size_t)stride, nb = sizeof(int) * (size_t)count,
+                 ob = sizeof(long long) * (size_t)(count + 1);
+    double *d_cells = nullptr;
+    int *d_n = nullptr;
+    long long *d_off = nullptr;
+    std::vector<long long> off((size_t)count + 1, 0);
+    off[0] = slot0;
+    hipError_t e = hipMalloc(&d_cells, cb);
+    if (e == hipSuccess) e = hipMalloc(&d_n, nb);
+    if (e == hipSuccess) e = hipMalloc(&d_off, ob);
+    if (e == hipSuccess) e = hipMemcpy(d_cells, cells, cb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_n, ncells, nb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_off, off.data(), ob, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = launch_history_pack(d_cells, (long long)stride, (long long)slot0, (long long)slot_cells, d_n,
+                                (long long)count, d_off, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(cells, d_cells, cb, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(off.data(), d_off, ob, hipMemcpyDeviceToHost);
+    if (d_cells) (void)hipFree(d_cells);
+    if (d_n) (void)hipFree(d_n);
+    if (d_off) (void)hipFree(d_off);
+    if (e != hipSuccess) return hip_err(nullptr, e, "tdt_history_pack");
+    for (int64_t i = 0; i <= count; ++i) off_out[i] = off[(size_t)i];
     return TD_OK;
 }
 

@@ -29,6 +29,18 @@ inline int64_t history_new_samples(int64_t iterations, int64_t first, int64_t ev
 int history_check_room(const td_history *h, int64_t added, int64_t cells_each, const char *who);
 // After a launch appended `added` samples: their offsets into the host mirror (one small copy).
 int history_adopt(td_history *h, int64_t added);
+// A recorded ladder's call (chain.cpp td_rounds_temper_recorded / td_rounds_exchange_recorded): its
+// `added` samples lie in slots of `cells_each` cells from the history's first free cell on, their headers
+// at samples, samples + 1, ...  Packs them in place (history_pack.hip; the context's stream, timer name
+// "history_pack"), forms their offsets on the device and adopts them.  The launch that wrote the slots
+// has ended.
+int history_pack_adopt(td_history *h, int64_t added, int64_t cells_each);
+// The pack kernel: `count` slots of S cells from cell slot0 of each of the four component arrays, ncells
+// [count] the cells each holds, off[0] = slot0 in place -> off[1 .. count].  kPackChunk: the cells one
+// round of its block moves (the tests cross it).
+constexpr int kPackChunk = 1024;
+hipError_t launch_history_pack(double *cells, long long stride, long long slot0, long long S, const int *ncells,
+                               long long count, long long *off, hipStream_t s);
 // One sample from host arrays (the HOST and DROPIN engines' loop): copies into the same buffers.
 int history_append_host(td_history *h, const double *x, const double *y, const double *z, const double *zeta,
                         int64_t ncells, double phi, int64_t iter, int action, int accept, const double *ptS);

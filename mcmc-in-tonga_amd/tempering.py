@@ -308,7 +308,7 @@ class TemperingLadder:
         self.decide_s += time.perf_counter() - t1
         return allphi
 
-    def run(self, rounds, k):
+    def run(self, rounds, k, history=None, first=1, every=1):
         """``rounds`` x ``step(k)``.  One process holding every replica in a
         resident launch (BASELINE config 4 on one GPU): the rounds and their
         swap steps run in the library (td_rounds_temper, td_swap_decide: the
@@ -316,10 +316,28 @@ class TemperingLadder:
         Python per round; the trace is the same.  With ``device_swaps`` the
         kernel itself decides the swaps (td_rounds_exchange): no host in the
         loop at all, across ranks through the library's RCCL allgathers; the
-        trace is again the same.  Returns the last gathered phis."""
+        trace is again the same.  Returns the last gathered phis.
+
+        ``history`` (a ``chain.History`` of the chains' context): the ladder's T = 1 ensemble -- after
+        each of the call's rounds number ``first``, ``first + every``, ... (1-based) the model of the
+        replica that ran the round at ladder level 0, taken before the round's swap step, is appended
+        to it where the kernel holds it (td_rounds_temper_recorded / td_rounds_exchange_recorded); the
+        history then feeds ``plot_model_hist``, ``credible_maps`` and the other ensemble consumers.
+        Nothing else changes (trajectories, trace, levels), and rounds split over several calls with
+        ``first`` carried over leave the history of one call.  Only a ladder whose rounds run in the
+        library records: ``ValueError`` where this call would fall back to ``step()`` (chains not
+        resident, or several ranks)."""
         rounds = int(rounds)
+        if history is not None:
+            if not (self.resident and self.ex.world == 1):
+                raise ValueError("TemperingLadder.run(history=...): needs the resident launch of one rank "
+                                 "(DEVICE chains of one context, resident=True, one process)")
+            if int(first) < 1 or int(every) < 1:
+                raise ValueError("TemperingLadder.run(history=...): need first >= 1, every >= 1")
+            if rounds <= 0:
+                return None
         if self.device_swaps and rounds > 0:
-            return self._run_exchange(rounds, k)
+            return self._run_exchange(rounds, k, history, first, every)
         if not (self.resident and self.ex.world == 1 and rounds > 0):
             out = None
             for _ in range(rounds):
@@ -340,9 +358,13 @@ class TemperingLadder:
         tried = np.zeros(max(R - 1, 1), dtype=np.int64)
         acc = np.zeros(max(R - 1, 1), dtype=np.int64)
         temps = np.ascontiguousarray(self.temps, dtype=np.float64)
-        check(lib().td_rounds_temper(self.rounds.h, rounds, int(k), ptr(temps), ptr(levels, _pi64), int(self.rnd),
-                                     ctypes.c_uint64(int(self.seed) & _M64), ptr(phis), ptr(lv_out, _pi64),
-                                     ptr(tried, _pi64), ptr(acc, _pi64)), self.chains[0].ctx.h)
+        args = (self.rounds.h, rounds, int(k), ptr(temps), ptr(levels, _pi64), int(self.rnd),
+                ctypes.c_uint64(int(self.seed) & _M64), ptr(phis), ptr(lv_out, _pi64), ptr(tried, _pi64),
+                ptr(acc, _pi64))
+        if history is None:
+            check(lib().td_rounds_temper(*args), self.chains[0].ctx.h)
+        else:
+            check(lib().td_rounds_temper_recorded(*args, int(first), int(every), history.h), self.chains[0].ctx.h)
         for j in range(rounds):
             self._trace.update(phis[j].tobytes())
             self._trace.update(lv_out[j].tobytes())
@@ -353,7 +375,7 @@ class TemperingLadder:
         self.rnd += rounds
         return phis[-1].copy()
 
-    def _run_exchange(self, rounds, k):
+    def _run_exchange(self, rounds, k, history=None, first=1, every=1):
         import ctypes
 
         from ._lib import _pi64, check, lib, ptr
@@ -371,10 +393,14 @@ class TemperingLadder:
         temps = np.ascontiguousarray(self.temps, dtype=np.float64)
         tm = np.zeros(7, dtype=np.float64)
         comm = self.ex.comm.h if self.ex.comm is not None else None
-        check(lib().td_rounds_exchange(self.rounds.h, comm, rounds, int(k), ptr(temps), ptr(levels, _pi64),
-                                       int(self.rnd), ctypes.c_uint64(int(self.seed) & _M64), ptr(phis),
-                                       ptr(lv_out, _pi64), ptr(tried, _pi64), ptr(acc, _pi64), ptr(tm)),
-              self.chains[0].ctx.h)
+        args = (self.rounds.h, comm, rounds, int(k), ptr(temps), ptr(levels, _pi64), int(self.rnd),
+                ctypes.c_uint64(int(self.seed) & _M64), ptr(phis), ptr(lv_out, _pi64), ptr(tried, _pi64),
+                ptr(acc, _pi64), ptr(tm))
+        if history is None:
+            check(lib().td_rounds_exchange(*args), self.chains[0].ctx.h)
+        else:
+            check(lib().td_rounds_exchange_recorded(*args, int(first), int(every), history.h),
+                  self.chains[0].ctx.h)
         for j in range(rounds):
             self._trace.update(phis[j].tobytes())
             self._trace.update(lv_out[j].tobytes())
