@@ -438,6 +438,50 @@ int td_history_convergence(td_ctx *ctx, td_history *const *hs, int64_t nh, const
                            const td_convergence *want);
 
 /* ------------------------------------------------------------------------
+ * Posterior volumes -- the numbers above at every node of a lattice
+ * xVec x yVec x zVec (or of any node list), whatever its size: what the
+ * posterior of a 3-D tomography is read, exported and compared as.
+ *   td_rasterize_volume takes td_rasterize's models (nchains / chain_len are
+ * read only with conv), td_history_volume the samples of the histories,
+ * history by history, where they lie (one history with samples = one chain;
+ * one without samples is skipped).  A lattice is sent x fastest.
+ *   Contract.  Every output at node q equals, bit for bit, what td_rasterize /
+ * td_rasterize_marginals / td_rasterize_convergence (or the td_history_*
+ * forms) return for the same models and that node: the nearest cell is the
+ * lexicographic minimum of (FP64 squared distance, cell index) below the 1e9
+ * sentinel, a NaN never wins, a model that answers nothing gives 0.0, and the
+ * statistics are those entry points' own kernels'.  values_out (nullable:
+ * small volumes, tests) is td_rasterize's value matrix [nmodels][nq]; marg
+ * (nullable) and conv (nullable) are td_marginals / td_convergence with
+ * quant_out [nprob][nq], hist_out [nq][nbins+3] and outputs [nq].
+ *   nq is 64-bit and no product nq x nmodels is formed in 32 bits; the only
+ * limit is memory (the outputs, the models and one slab).  One search
+ * structure is built for all models -- per model a bucket grid of about
+ * nCells / 2 buckets over the cells' box, the cells counting-sorted into one
+ * compact array of 32 B per cell -- and the nodes are swept in slabs of the
+ * largest multiple of 64 nodes whose value matrix fits 1 GiB (at least 64), so
+ * the value matrix never exists whole.  The results do not depend on the slab
+ * size, on the order the sort leaves inside a bucket, or on which sweep runs
+ * (models of few cells are swept by td_rasterize's brute-force kernel).
+ *   TD_ERR_ARG, before any HIP call (the message, which names the entry
+ * point, through td_last_error(NULL) without a context): vol NULL, nq < 0, a
+ * NULL qx / qy / qz / mean_out / std_out for nq > 0, what td_marginals and
+ * td_convergence reject (above), chain lengths that do not fit the models.
+ * nq == 0 returns TD_OK.  (csrc/volume.hip)
+ * ------------------------------------------------------------------------ */
+typedef struct td_volume {
+    const double *qx, *qy, *qz; int64_t nq;   /* any node list; a lattice is sent x fastest */
+    double *mean_out, *std_out;               /* [nq] */
+    double *values_out;                       /* [nmodels][nq], nullable (small volumes, tests) */
+    const td_marginals *marg;                 /* nullable; quant_out [nprob][nq], hist_out [nq][nbins+3] */
+    const td_convergence *conv;               /* nullable; outputs [nq] */
+} td_volume;
+int td_rasterize_volume(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const double *xCell,
+                        const double *yCell, const double *zCell, const double *zeta, int64_t nchains,
+                        const int64_t *chain_len /* used with conv */, const td_volume *vol);
+int td_history_volume(td_ctx *ctx, td_history *const *hs, int64_t nh, const td_volume *vol);
+
+/* ------------------------------------------------------------------------
  * Resident tempering rounds (parallel tempering; the reference's
  * chains are independent pmap workers, main_inversion.jl:15, so this is a new
  * capability): DEVICE chains of one context run in ONE launch that stays

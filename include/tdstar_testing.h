@@ -213,6 +213,24 @@ int tdt_convergence_plan(int64_t nchains, const int64_t *chain_len, int64_t max_
 int tdt_set_convergence_round(td_ctx *ctx, int64_t R);
 int tdt_set_convergence_lag_block(td_ctx *ctx, int LB);
 
+/* Posterior volumes (td_rasterize_volume).  tdt_volume_plan: what (nmodels, nq), the budget in bytes of a
+ * slab's value matrix (0: the default, 1 GiB) and a forced slab size (0: none) decide, out = {nodes per
+ * slab, slabs}: nodes = the largest multiple of 64 with 8 nmodels nodes <= budget (forced: rounded down to
+ * a multiple of 64), at least 64, at most 2^18 and 128 floor((2^31 - 1) / (8 ceil(nmodels / 8))) (one
+ * launch's blocks); pure host code.  tdt_set_volume_slab_nodes: force the slab size of later calls (0:
+ * auto).  tdt_set_volume_method: the sweep, 0 auto (bucket grids from a mean of 140 cells per model on),
+ * 1 bucket grids, 2 td_rasterize's brute-force kernel.  Same results whatever either is.
+ * tdt_volume_counters: the (model, node) pairs of the last call decided by the 3x3x3 block, by the 5x5x5
+ * block, by a full scan of the model, and by the brute-force kernel.  The three grid paths are counted by
+ * a second instance of the search kernel, which tdt_set_volume_counting(ctx, 1) selects for later calls
+ * (same values; its atomics on three shared words take longer than the search itself): a grid sweep
+ * without it reports -1, -1, -1. */
+int tdt_volume_plan(int64_t nmodels, int64_t nq, int64_t budget, int64_t forced, int64_t out[2]);
+int tdt_set_volume_slab_nodes(td_ctx *ctx, int64_t n);
+int tdt_set_volume_method(td_ctx *ctx, int method);
+int tdt_volume_counters(td_ctx *ctx, int64_t out[4]);
+int tdt_set_volume_counting(td_ctx *ctx, int on);
+
 /* Diagnostic: the nearest-cell search alone, `reps` back-to-back launches over
  * the context's ray points on the given cells (method as tdt_set_nn_method,
  * 1..3), timed by two HIP events; *us_out = microseconds per search. */

@@ -57,6 +57,12 @@ class TdConvergence(ctypes.Structure):
     _fields_ = [("max_lag", _i64), ("rhat_out", _vp), ("ess_out", _vp), ("lags_out", _vp)]
 
 
+class TdVolume(ctypes.Structure):
+    """td_volume; the arrays and the two optional requests as plain addresses (ptr(), ctypes.addressof)."""
+    _fields_ = [("qx", _vp), ("qy", _vp), ("qz", _vp), ("nq", _i64), ("mean_out", _vp), ("std_out", _vp),
+                ("values_out", _vp), ("marg", _vp), ("conv", _vp)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/*.h
 SIGNATURES = {
     "td_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _pd, _pd, _pd, _pd, _pd, _i64, _i64, _pd, _pd]),
@@ -120,7 +126,15 @@ SIGNATURES = {
                                                 _pd, _pd, ctypes.POINTER(TdConvergence)]),
     "td_history_convergence": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, _pd, _pd, _pd, _i64, _pd, _pd,
                                               ctypes.POINTER(TdConvergence)]),
+    "td_rasterize_volume": (ctypes.c_int, [_vp, _i64, _pi64, _pd, _pd, _pd, _pd, _i64, _pi64,
+                                           ctypes.POINTER(TdVolume)]),
+    "td_history_volume": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, ctypes.POINTER(TdVolume)]),
     # include/tdstar_testing.h
+    "tdt_volume_plan": (ctypes.c_int, [_i64, _i64, _i64, _i64, _pi64]),
+    "tdt_set_volume_slab_nodes": (ctypes.c_int, [_vp, _i64]),
+    "tdt_set_volume_method": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "tdt_volume_counters": (ctypes.c_int, [_vp, _pi64]),
+    "tdt_set_volume_counting": (ctypes.c_int, [_vp, ctypes.c_int]),
     "tdt_convergence_plan": (ctypes.c_int, [_i64, _pi64, _i64, _pi64, _pi64, _pd]),
     "tdt_set_convergence_round": (ctypes.c_int, [_vp, _i64]),
     "tdt_set_convergence_lag_block": (ctypes.c_int, [_vp, ctypes.c_int]),

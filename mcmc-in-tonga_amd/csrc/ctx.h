@@ -94,6 +94,15 @@ struct td_ctx {
     std::vector<double> mf_tS, mf_sig;  // what mf_dev holds
     double mf_likelihood = 0.0;
     std::string err;
+    // td_rasterize_volume / td_history_volume (volume.hip)
+    void *vol = nullptr;                // all models' cells SoA | offsets | boxes | grids | bucket prefix | path counters
+    size_t vol_cap = 0;                 // bytes
+    void *vol_grid = nullptr;           // bucket starts | cursors | the compact entries
+    size_t vol_grid_cap = 0;            // bytes
+    int64_t vol_slab_nodes = 0;         // nodes per slab, 0 auto (tdt_set_volume_slab_nodes)
+    int vol_method = 0;                 // the sweep: 0 auto, 1 bucket grids, 2 brute force (tdt_set_volume_method)
+    int vol_counting = 0;               // 1: the k_vol_search instance that counts its paths (tdt_set_volume_counting)
+    int64_t vol_counters[4] = {0, 0, 0, 0};  // the last call's (model, node) pairs per path (tdt_volume_counters)
 };
 
 namespace tdstar {

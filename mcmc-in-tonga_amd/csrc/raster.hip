@@ -22,6 +22,7 @@
 #include "ctx.h"
 #include "history.h"
 #include "marginals.h"
+#include "volume.h"
 
 namespace tdstar {
 
@@ -232,6 +233,29 @@ int tdstar::raster_reserve(td_ctx *ctx, size_t nd, size_t nh) {
         ctx->h_raster_cap = nh;
     }
     return TD_OK;
+}
+
+// volume.hip sweeps a slab of nodes with the same two kernels (volume.h)
+bool tdstar::raster_brute_fits(int64_t nmodels, int64_t nq) {
+    return (int64_t)kXcds * ((nmodels + kXcds - 1) / kXcds) * ((nq + kRasterNodes - 1) / kRasterNodes) <= INT32_MAX;
+}
+
+hipError_t tdstar::launch_raster_brute(const int64_t *cell_off_dev, const double *cells, int64_t cs, const double *q,
+                                       int nq, int nmodels, double *values, hipStream_t s, Timer *tm) {
+    hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
+    const int nchunks = (nq + kRasterNodes - 1) / kRasterNodes;
+    const int64_t blocks = (int64_t)kXcds * ((nmodels + kXcds - 1) / kXcds) * nchunks;
+    hipLaunchKernelGGL(k_raster_brute, dim3((unsigned)blocks), dim3(kRasterThreads), 0, s, cell_off_dev, cells, cs, q,
+                       nq, nmodels, nchunks, values);
+    if (tm) tm->end("raster_brute", t0, s);
+    return hipGetLastError();
+}
+
+hipError_t tdstar::launch_raster_stats(const double *values, int nmodels, int nq, double *mean, double *sd,
+                                       hipStream_t s) {
+    hipLaunchKernelGGL(k_raster_stats, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, values, nmodels, nq, mean,
+                       sd);
+    return hipGetLastError();
 }
 
 namespace {

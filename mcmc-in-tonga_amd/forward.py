@@ -295,6 +295,90 @@ class TdContext:
                                            ptr(std), ctypes.byref(w)), self.h)
         return dict(out, mean=mean, std=std)
 
+    VOL_AUTO, VOL_GRID, VOL_BRUTE = 0, 1, 2
+
+    def set_volume_slab_nodes(self, n):
+        """The nodes ``volume`` sweeps per slab (0: auto, what 1 GiB of values holds).  Same answer."""
+        check(lib().tdt_set_volume_slab_nodes(self.h, int(n)), self.h)
+
+    def set_volume_method(self, method):
+        """How ``volume`` sweeps a slab: VOL_AUTO (bucket grids unless the models are small), VOL_GRID,
+        VOL_BRUTE (``rasterize``'s kernel).  Same answer."""
+        check(lib().tdt_set_volume_method(self.h, int(method)), self.h)
+
+    def set_volume_counting(self, on):
+        """Run the instance of the search kernel that counts its paths (``volume_counters``); off by
+        default: its atomics cost more than the search.  Same answer."""
+        check(lib().tdt_set_volume_counting(self.h, int(bool(on))), self.h)
+
+    def volume_counters(self):
+        """The (model, node) pairs of the last ``volume`` call decided by the 3x3x3 block, the 5x5x5 block,
+        a full scan of the model (-1 each unless ``set_volume_counting(True)``), and the brute-force kernel."""
+        out = np.zeros(4, dtype=np.int64)
+        check(lib().tdt_volume_counters(self.h, ptr(out, _lib._pi64)), self.h)
+        return tuple(int(v) for v in out)
+
+    @staticmethod
+    def volume_plan(nmodels, nq, budget=0, forced=0):
+        """(nodes per slab, slabs) of a ``volume`` call (budget in bytes, 0: 1 GiB); needs no GPU."""
+        out = np.zeros(2, dtype=np.int64)
+        check(lib().tdt_volume_plan(int(nmodels), int(nq), int(budget), int(forced), ptr(out, _lib._pi64)))
+        return int(out[0]), int(out[1])
+
+    def _volume(self, call, nmodels, qx, qy, qz, probs, bins, conv, max_lag, want_values):
+        """The td_volume request around ``call(byref(vol))`` -> dict of the outputs asked for."""
+        qx, qy, qz = (f64(np.ravel(a)) for a in (qx, qy, qz))
+        nq = len(qx)
+        if not (len(qy) == len(qz) == nq):
+            raise ValueError("qx, qy and qz must have the same length")
+        mean, std = np.empty(nq), np.empty(nq)
+        vals = np.empty((nmodels, nq)) if want_values else None
+        out = dict(mean=mean, std=std, values=vals, quantiles=None, hist=None)
+        held = []
+        marg = cw = None
+        if len(np.ravel(probs)) or bins is not None:
+            marg, arrays, out["quantiles"], out["hist"] = self._marginals_want(nq, probs, bins)
+            held.append(arrays)
+        if conv:
+            cw, arrays = self._convergence_want(nq, max_lag, self.CONV_ALL)
+            out.update(arrays)
+        vol = _lib.TdVolume(ptr(qx), ptr(qy), ptr(qz), nq, ptr(mean), ptr(std), ptr(vals),
+                            ctypes.addressof(marg) if marg is not None else None,
+                            ctypes.addressof(cw) if cw is not None else None)
+        call(ctypes.byref(vol))
+        del held
+        return out
+
+    def volume(self, models, qx, qy, qz, probs=(), bins=None, chain_len=None, max_lag=0, want_values=False):
+        """td_rasterize_volume: ``rasterize`` / ``marginals`` / ``convergence_models`` in one call at ANY
+        number of nodes (a whole lattice, x fastest): one search structure for all models, the nodes swept
+        slab by slab.  -> dict(mean[nq], std[nq], values[nmodels, nq] or None, quantiles[nprob, nq] or
+        None, hist[nq, nbins + 3] or None and, with ``chain_len`` (the rows of each chain), rhat, ess,
+        lags [nq]); every number is the section calls', bit for bit.  models as for ``rasterize``."""
+        off = np.zeros(len(models) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(m[0]) for m in models])
+        cat = [f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) for k in range(4)]
+        lens = np.ascontiguousarray(chain_len, dtype=np.int64).ravel() if chain_len is not None else None
+
+        def call(vol):
+            check(lib().td_rasterize_volume(self.h, len(models), ptr(off, _lib._pi64), *(ptr(c) for c in cat),
+                                            len(lens) if lens is not None else 0, ptr(lens, _lib._pi64), vol), self.h)
+
+        return self._volume(call, len(models), qx, qy, qz, probs, bins, lens is not None, max_lag, want_values)
+
+    def volume_history(self, histories, qx, qy, qz, probs=(), bins=None, convergence=False, max_lag=0,
+                       want_values=False):
+        """td_history_volume: ``volume`` on the samples of the histories (chain.History) where they lie;
+        with ``convergence`` one history is one chain (one without samples is skipped)."""
+        histories = list(histories)
+        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
+        nm = sum(len(h) for h in histories)
+
+        def call(vol):
+            check(lib().td_history_volume(self.h, hs, len(histories), vol), self.h)
+
+        return self._volume(call, nm, qx, qy, qz, probs, bins, convergence, max_lag, want_values)
+
     def interpolate(self, cells, X, Y, Z, want_nearest=False):
         """-> (zeta[npoints], nearest[npoints] or None)"""
         xc, yc, zc, ze = (f64(c) for c in cells)

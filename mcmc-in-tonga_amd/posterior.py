@@ -180,6 +180,52 @@ def convergence_maps(model_hist, dataStruct, TD_parameters, max_lag=0):
     return maps
 
 
+def posterior_volume(model_hist, dataStruct, TD_parameters, probs=(0.05, 0.5, 0.95), bins=None, convergence=False,
+                     max_lag=0, xs=None, ys=None, zs=None):
+    """The posterior as a volume: what ``plot_model_hist``, ``credible_maps`` and ``convergence_maps`` give
+    section by section, at every node of the lattice ``xs`` x ``ys`` x ``zs`` (default: dataStruct.xVec /
+    yVec / zVec) in one call, as [nx, ny, nz] arrays -- ``mean``, ``std``, ``masked`` (mean where std <= 5,
+    NaN elsewhere), ``quantiles`` [nprob, nx, ny, nz] and ``width`` (the last minus the first quantile),
+    ``hist`` [nx, ny, nz, nbins + 3] with ``bins`` = (nbins, lo, hi) and, with ``convergence``, ``rhat``,
+    ``ess``, ``lags`` and ``summary`` as in ``convergence_maps``; ``x``, ``y``, ``z``: the lattice vectors.
+    ``vol["mean"][:, j, :]`` is the xz section at ys[j], ``[:, :, k]`` the xy section at zs[k], bit for bit.
+    Same inputs as ``plot_model_hist`` (Models, nested lists, a ``History`` or a list of them); computed on
+    the device slab by slab, whatever the lattice's size (td_rasterize_volume / td_history_volume)."""
+    ctx = context_for(dataStruct)  # (TD_parameters: the siblings' signature; the lattice decides everything here)
+    xv, yv, zv = (np.asarray(v if v is not None else d, dtype=np.float64).ravel()
+                  for v, d in ((xs, dataStruct.xVec), (ys, dataStruct.yVec), (zs, dataStruct.zVec)))
+    shape = (len(zv), len(yv), len(xv))  # x fastest
+    qx = np.tile(xv, len(yv) * len(zv))
+    qy = np.tile(np.repeat(yv, len(xv)), len(zv))
+    qz = np.repeat(zv, len(xv) * len(yv))
+    models, lens = _chains(model_hist)
+    if _on_device(models):
+        r = ctx.volume_history(models, qx, qy, qz, probs, bins, convergence, max_lag)
+    else:
+        r = ctx.volume([m.cells() for m in models], qx, qy, qz, probs, bins, lens if convergence else None, max_lag)
+    out = {"x": xv, "y": yv, "z": zv}
+    for f in ("mean", "std") + (("rhat", "ess", "lags") if convergence else ()):
+        out[f] = r[f].reshape(shape).transpose(2, 1, 0).copy()
+    out["masked"] = np.where(out["std"] > 5, np.nan, 1.0) * out["mean"]
+    q = r["quantiles"]
+    if q is not None:
+        out["quantiles"] = q.reshape((len(q),) + shape).transpose(0, 3, 2, 1).copy()
+        out["width"] = out["quantiles"][-1] - out["quantiles"][0]
+    if r["hist"] is not None:
+        out["hist"] = r["hist"].reshape(shape + (r["hist"].shape[1],)).transpose(2, 1, 0, 3).copy()
+    if convergence:
+        rhat, ess = r["rhat"], r["ess"]
+        with np.errstate(invalid="ignore"):
+            out["summary"] = {
+                "rhat_max": float(np.nanmax(rhat)) if not np.all(np.isnan(rhat)) else float("nan"),
+                "ess_min": float(np.nanmin(ess)) if not np.all(np.isnan(ess)) else float("nan"),
+                "frac_rhat_above_1_01": float(np.mean(rhat > 1.01)),
+                "frac_capped": float(np.mean(r["lags"] < 0)),
+                "nan_columns": int(np.sum(np.isnan(rhat) | np.isnan(ess))),
+                "n": min(lens) // 2, "m": 2 * len(lens)}
+    return out
+
+
 def trace_diagnostics(histories, max_lag=0):
     """R-hat / ESS / lags of the two scalar traces of a ``History`` or a list of them (one chain each):
     {"phi": {rhat, ess, lags}, "ncells": {...}}, through td_convergence_values with two columns."""
