@@ -54,6 +54,9 @@ int tdt_chain_variant(const int64_t in[15], int64_t out[8]);
  * recorded ladder's (td_rounds_temper_recorded / td_rounds_exchange_recorded; it counts with in[10] or in[11]
  * set).  Its instances sit at table positions >= 12. */
 int tdt_chain_variant_rounds(const int64_t in[15], int rounds_rec, int64_t out[8]);
+/* Launches of each k_chain_run instance by this process since it started: out[i] for table position i,
+ * *n = the table's length (out has room for 32).  Host only. */
+int tdt_chain_launch_counts(int64_t out[32], int *n);
 /* The pack kernel of a recorded ladder (csrc/history_pack.hip) on caller-given slots: cells = host [4][stride]
  * (x, y, z, zeta rows), `count` slots of slot_cells cells from cell slot0 of every row, ncells[count] the cells
  * each slot holds (0 .. slot_cells).  On return the samples lie packed from slot0 on in every row (the cells

@@ -836,6 +836,13 @@ int tdt_chain_variant_rounds(const int64_t in[15], int rounds_rec, int64_t out[8
     return TD_OK;
 }
 
+int tdt_chain_launch_counts(int64_t out[32], int *n) {
+    if (!out || !n) return TD_ERR_ARG;
+    std::memset(out, 0, 32 * sizeof(int64_t));
+    *n = chain_launch_counts(out, 32);
+    return TD_OK;
+}
+
 int tdt_set_nn_method(td_ctx *ctx, int method) {
     if (!ctx || method < 0 || method > 3) return TD_ERR_ARG;
     ctx->nn_method = method == 3 ? 1 : method;  // 3: brute force through the split search

@@ -306,6 +306,9 @@ hipError_t chain_run(const DevChain *host, const DevChain *dev, int nchains, int
                      int num_cus = 0);  // > 0: a batch of more chains than CUs packs two per CU
 // The k_chain_run instance chain_run launches for `v`: its index in chain_run's table, -1 if none (host only)
 int chain_variant_index(const ChainVariant &v);
+// chain_run's launches of each table entry by this process: out[i] for i < min(cap, the table's length), which
+// it returns (host only)
+int chain_launch_counts(int64_t *out, int cap);
 // Testing: the chain's chi^2 code on a caller-given ptS (n <= 4096) --
 // path 2: k_chi2_prefix (the starting state's sequential prefix sums, what
 // chain_full_state runs), 3: the proposal-time sum (the terms of MCsub.jl:171,

@@ -39,6 +39,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <climits>
 #include <cstddef>
 #include <cstdlib>
@@ -1707,6 +1708,7 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
                             }
                         }
                         __syncthreads();
+                        SKEW(21);
                     }
                 }
             } else {  // rejected: flags down, the changed rays get their old chi^2 terms back
@@ -2006,6 +2008,16 @@ int chain_variant_index(const ChainVariant &v) {
     return -1;
 }
 
+// Launches of each table entry by this process (host only; testing: a case that means to run one
+// instance can tell that it did, tdt_chain_launch_counts)
+static std::atomic<int64_t> g_launches[sizeof(kChainInstances) / sizeof(kChainInstances[0])];
+
+int chain_launch_counts(int64_t *out, int cap) {
+    const int n = (int)(sizeof(kChainInstances) / sizeof(kChainInstances[0]));
+    for (int i = 0; i < n && i < cap; ++i) out[i] = g_launches[i].load(std::memory_order_relaxed);
+    return n;
+}
+
 hipError_t chain_run(const DevChain *host, const DevChain *dev, int nchains, int64_t iters, hipStream_t s,
                      const ScriptArgs *script, DrawsBuf db, int num_cus) {
     ScriptArgs sa{};
@@ -2064,6 +2076,7 @@ hipError_t chain_run(const DevChain *host, const DevChain *dev, int nchains, int
     }
     const int at = chain_variant_index(c.v);
     if (at < 0) return hipErrorInvalidValue;  // no such instance: never another kernel in its place
+    g_launches[at].fetch_add(1, std::memory_order_relaxed);
     hipLaunchKernelGGL(kChainInstances[at].k, dim3(grid), dim3(c.v.nth), c.lds, s, dev, (long long)iters, sa);
     return hipGetLastError();
 }

@@ -320,3 +320,70 @@ def test_td_info_layout_matches_header():
     assert int(re.search(r"#define TDSTAR_ABI_VERSION (\d+)", hdr).group(1)) == 2
     assert [f for f, _ in _lib.TdInfo._fields_][-1] == "num_cus"
     assert ctypes.sizeof(_lib.TdInfo) == 4 + 4 + 8 * 4 + 8 + 32 + 4 + 4  # (tail padding to 8)
+
+
+# ------------------------------------- the skew cases of the chain kernel's instances ----
+def test_every_chain_instance_has_a_skew_case():
+    """tdt_chain_launch_counts in a process that launched nothing (a fresh child: this one may have run GPU
+    tests): one zero per entry of the launcher's table -- and every entry is some skew case's target
+    (tests/test_gpu_skew_instances.py), so a fifteenth instance fails here until it has one."""
+    import subprocess
+    import sys
+
+    import test_gpu_skew_instances as sk
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import ctypes, json, sys; sys.path.insert(0, %r); import tonga; L = tonga.load().lib();"
+            "out = (ctypes.c_int64 * 32)(*([7] * 32)); n = ctypes.c_int(-1);"
+            "rc = L.tdt_chain_launch_counts(out, ctypes.byref(n));"
+            "bad = L.tdt_chain_launch_counts(None, ctypes.byref(n)), L.tdt_chain_launch_counts(out, None);"
+            "print(json.dumps([rc, n.value, list(out), list(bad)]))" % root)
+    p = subprocess.run([sys.executable, "-c", code], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
+    assert p.returncode == 0, p.stdout.decode(errors="replace")[-2000:]
+    import json
+    rc, n, out, bad = json.loads(p.stdout.decode().splitlines()[-1])
+    assert rc == 0 and n == 14 and out == [0] * 32 and bad == [1, 1]  # (TD_ERR_ARG)
+    assert sk.TARGETS == list(range(n)) and len(sk.TARGETS) == 14
+    assert sorted(sk.CREDITED) == [0, 8, 12]  # the three older workers' instances, credited by name
+    for name in sk.CREDITED.values():
+        assert os.path.exists(os.path.join(root, name)), name
+    assert sorted(sum((sk.group(g) for g in ("hbm", "packed", "scripted", "rounds")), [])) == sorted(sk.CASES)
+
+
+def test_skew_case_judge_rejects_bad_rows():
+    """The check that tests/test_gpu_skew_instances.py can fail: its judgement of the worker's rows, on
+    made-up rows."""
+    import test_gpu_skew_instances as sk
+
+    def row(name, **over):
+        target, _, need = sk.CASES[name]
+        launched = [0] * 14
+        launched[target] = 2
+        r = {"case": name, "same": True, "why": None, "guard": 0, "sites": None, "launched": launched,
+             "twin_launched": 0, "accepted": [3, 1, 4, 2], "swaps": 2, "long_shifts": 2}
+        r.update(over)
+        return r
+
+    names = sk.group("hbm")
+    assert names == ["hbm_free", "hbm_rb", "rec_hbm"]
+    good = [row(n) for n in names]
+    assert sk.judge(good, names) == []
+    elsewhere = [0] * 14
+    elsewhere[0] = 5  # instance 0 again, not the target
+    for bad_row, word in ((row("hbm_free", same=False, why="phi"), "differs"),
+                          (row("hbm_free", guard=1000, sites=[1] * 9), "gave up"),
+                          (row("hbm_free", launched=elsewhere), "never launched"),
+                          (row("hbm_free", launched=[]), "never launched"),
+                          (row("hbm_free", twin_launched=3), "reference launched"),
+                          (row("hbm_free", accepted=[3, 0, 4, 2]), "accepted"),
+                          (row("hbm_free", accepted=None), "accepted"),
+                          (row("hbm_free", long_shifts=1), "long_shifts"),
+                          (row("hbm_rb", swaps=0), "swaps"),
+                          (row("rec_hbm", same=None), "differs")):
+        rows = [bad_row if r["case"] == bad_row["case"] else r for r in good]
+        bad = sk.judge(rows, names)
+        assert len(bad) == 1 and word in bad[0], (bad_row, bad)
+    assert any("rec_hbm: 0 rows" in b for b in sk.judge(good[:2], names))  # a missing case
+    assert any("2 rows" in b for b in sk.judge(good + [good[0]], names))  # a case twice
+    assert any("not asked for" in b for b in sk.judge(good + [row("xch_lds")], names))
+    assert sk.judge([], names) != []
