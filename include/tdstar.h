@@ -482,6 +482,56 @@ int td_rasterize_volume(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, c
 int td_history_volume(td_ctx *ctx, td_history *const *hs, int64_t nh, const td_volume *vol);
 
 /* ------------------------------------------------------------------------
+ * Posterior predictive data -- whether an ensemble fits the data, ray by ray,
+ * and predicts data it was not fitted to: every model's predicted t* on the
+ * rays of ctx, its chi^2 against ctx's tS / allSig, and the statistics of the
+ * matrix ptS[nmodels][n] over the models, in one sweep on the device.
+ *   td_rasterize_predict takes td_rasterize's models (nchains / chain_len are
+ * read only with conv), td_history_predict the samples of the histories,
+ * history by history, where they lie (one history with samples = one chain;
+ * one without samples is skipped).  The context names the rays -- they may be
+ * a held-out set, re-picked data or another allSig -- and the histories name
+ * the ensemble: a history need NOT belong to ctx, it must only live on ctx's
+ * device (else TD_ERR_ARG); only its cell buffers and offsets are read.
+ *   Contract.  Row k of ptS_out and phi_out[k] equal td_evaluate of model k on
+ * ctx, bit for bit: the nearest cell of a ray point is the lexicographic
+ * minimum of (FP64 squared distance, cell index) below the 1e9 sentinel, a NaN
+ * never wins, a point with no answer takes zeta = 0; a ray's segment terms and
+ * their sum are td_evaluate's (Julia's Base.sum association, every length
+ * class); chi^2 is the sequential sum in ray order (MCsub.jl:170-172, see
+ * td_misfit; td_set_sigma is honoured).  A model of 0 cells and a context of
+ * 0 rays give what td_evaluate_batch gives.  mean_out / std_out, marg and conv
+ * are td_rasterize's, td_marginals' and td_convergence's own kernels on the
+ * matrix ptS[nmodels][n] as a value matrix (column = ray): their numbers are
+ * what td_convergence_values and the section calls return for that matrix.
+ *   No product of models x points or models x rays is formed in 32 bits; a ray
+ * of more than 2^18 points is TD_ERR_ARG; the only other limit is memory (the
+ * models, ptS[nmodels][n] and one slab).  The search structure is the posterior
+ * volumes' (one bucket grid per model, built once; tdt_set_volume_method is
+ * honoured), the queries are ctx's ray points, already on the device, swept in
+ * slabs of whole rays and, where the budget asks for it, in chunks of models.
+ * The results depend on neither.
+ *   TD_ERR_ARG, before any HIP call (the message, which names the entry
+ * point, through td_last_error(NULL) without a context), in this order: out
+ * NULL; nothing asked for (every output NULL, no marg, no conv); only one of
+ * mean_out / std_out; what td_marginals and td_convergence reject (above);
+ * offsets not monotone; chain lengths that do not fit the models; no model or
+ * no sample in all; ctx NULL.  (csrc/predict.hip)
+ * ------------------------------------------------------------------------ */
+typedef struct td_predict {
+    double *ptS_out;              /* [nmodels][n], nullable: every model's predicted t* (row k = model k)       */
+    double *phi_out;              /* [nmodels], nullable: every model's sequential chi^2 against the context's  */
+                                  /*            tS / allSig (td_set_sigma is honoured)                          */
+    double *mean_out, *std_out;   /* [n], nullable (both or neither): over the models, per ray                  */
+    const td_marginals *marg;     /* nullable; quant_out [nprob][n], hist_out [n][nbins+3]                      */
+    const td_convergence *conv;   /* nullable; outputs [n] (R-hat / ESS of each ray's predicted t*)             */
+} td_predict;
+int td_rasterize_predict(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const double *xCell,
+                         const double *yCell, const double *zCell, const double *zeta, int64_t nchains,
+                         const int64_t *chain_len /* used with conv */, const td_predict *out);
+int td_history_predict(td_ctx *ctx, td_history *const *hs, int64_t nh, const td_predict *out);
+
+/* ------------------------------------------------------------------------
  * Resident tempering rounds (parallel tempering; the reference's
  * chains are independent pmap workers, main_inversion.jl:15, so this is a new
  * capability): DEVICE chains of one context run in ONE launch that stays

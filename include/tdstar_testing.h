@@ -234,6 +234,23 @@ int tdt_set_volume_method(td_ctx *ctx, int method);
 int tdt_volume_counters(td_ctx *ctx, int64_t out[4]);
 int tdt_set_volume_counting(td_ctx *ctx, int on);
 
+/* Posterior predictive data (td_rasterize_predict).  tdt_predict_plan: what nmodels, the n rays' point
+ * counts ray_points[n], the budget in bytes of a slab's value matrix (0: the default, 1 GiB) and the forced
+ * sizes (0: none) decide; pure host code.  out = {points, chunk, slabs}: a slab is a run of whole
+ * consecutive rays of at most `points` points in all and at most 2^20 rays, filled greedily ray after ray;
+ * points = the largest multiple of 64 with 8 nmodels points <= budget (forced_points: rounded down to a
+ * multiple of 64), at least 64, raised to the longest ray rounded up to 64, at most 2^18; the models are
+ * swept `chunk` at a time: forced_chunk, else max(1, budget / (8 points)); at most nmodels and 2^19.
+ * edges (nullable, room for n + 1): edges[k] .. edges[k + 1] are slab k's rays ({0} without rays).
+ * TD_ERR_ARG for a ray of more than 2^18 points.  tdt_set_predict_plan: force both for later calls (0:
+ * auto).  tdt_set_predict_placement: 1 runs the workgroups of model m of the ray-sum kernel on XCD m % 8
+ * (0, the default: a model's workgroups follow each other).  Same results whatever any of them is.
+ * tdt_volume_counters also reports a predictive call's sweeps. */
+int tdt_predict_plan(int64_t nmodels, int64_t n, const int64_t *ray_points, int64_t budget, int64_t forced_points,
+                     int64_t forced_chunk, int64_t out[3], int64_t *edges);
+int tdt_set_predict_plan(td_ctx *ctx, int64_t slab_points, int64_t model_chunk);
+int tdt_set_predict_placement(td_ctx *ctx, int xcd);
+
 /* Diagnostic: the nearest-cell search alone, `reps` back-to-back launches over
  * the context's ray points on the given cells (method as tdt_set_nn_method,
  * 1..3), timed by two HIP events; *us_out = microseconds per search. */

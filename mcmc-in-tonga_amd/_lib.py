@@ -63,6 +63,11 @@ class TdVolume(ctypes.Structure):
                 ("values_out", _vp), ("marg", _vp), ("conv", _vp)]
 
 
+class TdPredict(ctypes.Structure):
+    """td_predict; the arrays and the two optional requests as plain addresses (ptr(), ctypes.addressof)."""
+    _fields_ = [("ptS_out", _vp), ("phi_out", _vp), ("mean_out", _vp), ("std_out", _vp), ("marg", _vp), ("conv", _vp)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/*.h
 SIGNATURES = {
     "td_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _pd, _pd, _pd, _pd, _pd, _i64, _i64, _pd, _pd]),
@@ -129,7 +134,13 @@ SIGNATURES = {
     "td_rasterize_volume": (ctypes.c_int, [_vp, _i64, _pi64, _pd, _pd, _pd, _pd, _i64, _pi64,
                                            ctypes.POINTER(TdVolume)]),
     "td_history_volume": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, ctypes.POINTER(TdVolume)]),
+    "td_rasterize_predict": (ctypes.c_int, [_vp, _i64, _pi64, _pd, _pd, _pd, _pd, _i64, _pi64,
+                                            ctypes.POINTER(TdPredict)]),
+    "td_history_predict": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, ctypes.POINTER(TdPredict)]),
     # include/tdstar_testing.h
+    "tdt_predict_plan": (ctypes.c_int, [_i64, _i64, _pi64, _i64, _i64, _i64, _pi64, _pi64]),
+    "tdt_set_predict_plan": (ctypes.c_int, [_vp, _i64, _i64]),
+    "tdt_set_predict_placement": (ctypes.c_int, [_vp, ctypes.c_int]),
     "tdt_volume_plan": (ctypes.c_int, [_i64, _i64, _i64, _i64, _pi64]),
     "tdt_set_volume_slab_nodes": (ctypes.c_int, [_vp, _i64]),
     "tdt_set_volume_method": (ctypes.c_int, [_vp, ctypes.c_int]),

@@ -15,6 +15,7 @@
 
 #include "chain_dev.h"
 #include "ctx.h"
+#include "predict.h"
 #include "volume.h"
 
 namespace {
@@ -304,6 +305,7 @@ void free_ctx(td_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     shadow_free(c);
     volume_free(c);
+    predict_free(c);
     c->timer.release();
     void *dev[] = {c->g.px, c->g.py, c->g.pz, c->g.w, c->g.ray_off, c->g.tS, c->g.sig, c->g.terms, c->cells,
                    c->nn.part_d, c->nn.part_i, c->best_i, c->best_d, c->zeta0, c->phi,

@@ -103,6 +103,12 @@ struct td_ctx {
     int vol_method = 0;                 // the sweep: 0 auto, 1 bucket grids, 2 brute force (tdt_set_volume_method)
     int vol_counting = 0;               // 1: the k_vol_search instance that counts its paths (tdt_set_volume_counting)
     int64_t vol_counters[4] = {0, 0, 0, 0};  // the last call's (model, node) pairs per path (tdt_volume_counters)
+    // td_rasterize_predict / td_history_predict (predict.hip)
+    void *pred = nullptr;               // ptS [nmodels][n] | phi [nmodels] | mean, std [n]
+    size_t pred_cap = 0;                // bytes
+    int64_t pred_slab_points = 0;       // points per slab, 0 auto (tdt_set_predict_plan)
+    int64_t pred_model_chunk = 0;       // models per sweep, 0 auto (tdt_set_predict_plan)
+    int pred_placement = 0;             // k_pred_ray_sums: 0 a model's blocks follow each other, 1 on XCD m % 8
 };
 
 namespace tdstar {

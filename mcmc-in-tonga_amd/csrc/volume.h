@@ -3,8 +3,11 @@
 // slab by slab (include/tdstar.h "Posterior volumes").
 #pragma once
 #include <cstdint>
+#include <vector>
 
 #include "ctx.h"
+
+struct td_history;
 
 namespace tdstar {
 
@@ -28,6 +31,32 @@ bool raster_brute_fits(int64_t nmodels, int64_t nq);
 hipError_t launch_raster_brute(const int64_t *cell_off_dev, const double *cells, int64_t cs, const double *q, int nq,
                                int nmodels, double *values, hipStream_t s, Timer *tm);
 hipError_t launch_raster_stats(const double *values, int nmodels, int nq, double *mean, double *sd, hipStream_t s);
+
+// The search structure of one call, built once for all models in ctx->vol / ctx->vol_grid (volume.hip:
+// k_vol_boxes, the host's make_cell_grid per model, k_vol_grid_build; models of few cells are swept by
+// k_raster_brute and get no grids), and the sweep of a device query block against it.  The volume entry
+// points and the posterior predictive ones (predict.hip) share both.
+struct VolSearch {
+    int64_t nmodels = 0, cs = 1;  // cs: the SoA stride of cells
+    bool grid = false;            // bucket grids (k_vol_search), else k_raster_brute
+    double *cells = nullptr;      // x | y | z | zeta of every model behind one another
+    int64_t *off = nullptr;       // [nmodels + 1] the models' first cells
+    CellGrid *grids = nullptr;    // [nmodels]
+    int64_t *boff = nullptr;      // [nmodels + 1] the models' first bucket starts
+    int *start = nullptr;
+    BucketEntry *ent = nullptr;
+    unsigned long long *counters = nullptr;  // the paths k_vol_search<true> counts
+    std::vector<CellGrid> grids_host;        // what grids and boff were copied from
+    std::vector<int64_t> boff_host;
+};
+// segs == nullptr: the cells are the host arrays; else the histories' packed samples (any context's, on
+// ctx's device), cell_off the concatenation's host prefix.  Every argument has been checked.
+int volume_build(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *cell_off, const double *xCell,
+                 const double *yCell, const double *zCell, const double *zeta, const std::vector<td_history *> *segs,
+                 VolSearch *out);
+// values[nm][ns] = the nearest cell's zeta of the models [m0, m0 + nm) at the device queries q = [3][ns],
+// ns >= 1 (timers vol_search / raster_brute)
+int volume_sweep(td_ctx *ctx, const VolSearch &S, int64_t m0, int64_t nm, const double *q, int64_t ns, double *values);
 
 // td_destroy: the volume workspaces of a context
 void volume_free(td_ctx *ctx);

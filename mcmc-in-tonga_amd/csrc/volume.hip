@@ -279,14 +279,17 @@ CellGrid one_bucket_grid() {
     return G;
 }
 
-// td_rasterize_volume (segs == nullptr: the cells are the host arrays) and td_history_volume (the cells
-// are the histories' packed samples, copied device to device behind one another; cell_off is the
+}  // namespace
+
+// The search structure of td_rasterize_volume / td_history_volume and of the posterior predictive calls
+// (predict.hip), in ctx's volume workspaces: segs == nullptr: the cells are the host arrays; else they are
+// the histories' packed samples, copied device to device behind one another (cell_off is the
 // concatenation's host prefix).  Every argument has been checked.
-int volume_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *cell_off, const double *xCell,
-                const double *yCell, const double *zCell, const double *zeta, const std::vector<td_history *> *segs,
-                int64_t nchains, const int64_t *chain_len, const td_volume *vol) {
+int volume_build(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *cell_off, const double *xCell,
+                 const double *yCell, const double *zCell, const double *zeta, const std::vector<td_history *> *segs,
+                 VolSearch *out) {
     const std::string w(who);
-    const int64_t nq = vol->nq, total = cell_off[nmodels], cs = std::max<int64_t>(total, 1);
+    const int64_t total = cell_off[nmodels], cs = std::max<int64_t>(total, 1);
     if (nmodels > INT32_MAX - 64) return set_err(ctx, TD_ERR_ARG, w + ": too many models");
     for (int64_t k = 0; k < nmodels; ++k)
         if (cell_off[k + 1] - cell_off[k] > INT32_MAX) return set_err(ctx, TD_ERR_ARG, w + ": a model of too many cells");
@@ -325,8 +328,8 @@ int volume_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *ce
     int *dstart = nullptr;
     BucketEntry *dent = nullptr;
     std::vector<double> boxes;
-    std::vector<CellGrid> grids;
-    std::vector<int64_t> boff;
+    std::vector<CellGrid> &grids = out->grids_host;  // (the sources of asynchronous copies: they live as long as the sweeps)
+    std::vector<int64_t> &boff = out->boff_host;
     if (grid) {
         hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
         hipLaunchKernelGGL(k_vol_boxes, dim3((unsigned)nmodels), dim3(kVolThreads), 0, s, doff, dc, cs, dbox);
@@ -360,6 +363,53 @@ int volume_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *ce
         if (tm) tm->end("vol_grid_build", t0, s);
         TD_HIP(ctx, hipGetLastError());
     }
+    out->nmodels = nmodels;
+    out->cs = cs;
+    out->grid = grid;
+    out->cells = dc;
+    out->off = doff;
+    out->grids = dgrid;
+    out->boff = dboff;
+    out->start = dstart;
+    out->ent = dent;
+    out->counters = dcount;
+    return TD_OK;
+}
+
+// One slab's sweep: values[nm][ns] of the models [m0, m0 + nm) at the device query block q = [3][ns].
+int volume_sweep(td_ctx *ctx, const VolSearch &S, int64_t m0, int64_t nm, const double *q, int64_t ns, double *values) {
+    hipStream_t s = ctx->stream;
+    Timer *tm = ctx->timer.on ? &ctx->timer : nullptr;
+    if (S.grid) {
+        const int nchunks = (int)((ns + kVolThreads - 1) / kVolThreads);
+        const int64_t blocks = (int64_t)kVolXcds * ((nm + kVolXcds - 1) / kVolXcds) * nchunks;
+        hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
+        if (ctx->vol_counting)
+            hipLaunchKernelGGL(k_vol_search<true>, dim3((unsigned)blocks), dim3(kVolThreads), 0, s, S.off + m0, S.cells, S.cs,
+                               S.grids + m0, S.boff + m0, S.start, S.ent, q, (int)ns, (int)nm, nchunks, values, S.counters);
+        else
+            hipLaunchKernelGGL(k_vol_search<false>, dim3((unsigned)blocks), dim3(kVolThreads), 0, s, S.off + m0, S.cells, S.cs,
+                               S.grids + m0, S.boff + m0, S.start, S.ent, q, (int)ns, (int)nm, nchunks, values, S.counters);
+        if (tm) tm->end("vol_search", t0, s);
+        TD_HIP(ctx, hipGetLastError());
+    } else {
+        TD_HIP(ctx, launch_raster_brute(S.off + m0, S.cells, S.cs, q, (int)ns, (int)nm, values, s, tm));
+    }
+    return TD_OK;
+}
+
+namespace {
+
+// td_rasterize_volume and td_history_volume (volume_build's arguments).
+int volume_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *cell_off, const double *xCell,
+                const double *yCell, const double *zCell, const double *zeta, const std::vector<td_history *> *segs,
+                int64_t nchains, const int64_t *chain_len, const td_volume *vol) {
+    VolSearch S;
+    if (int rc = volume_build(ctx, who, nmodels, cell_off, xCell, yCell, zCell, zeta, segs, &S)) return rc;
+    const int64_t nq = vol->nq;
+    const bool grid = S.grid;
+    hipStream_t s = ctx->stream;
+    unsigned long long *dcount = S.counters;
     // the slabs: queries [3][ns] | V_slab [nmodels][ns] | mean, std [ns]; pinned: queries | quantile rows
     const VolPlan plan = volume_plan(nmodels, nq, kVolDefaultBudget, ctx->vol_slab_nodes);
     const int64_t cap = std::min(plan.nodes, nq);
@@ -374,22 +424,8 @@ int volume_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *ce
         std::memcpy(h + ns, vol->qy + q0, sizeof(double) * (size_t)ns);
         std::memcpy(h + 2 * ns, vol->qz + q0, sizeof(double) * (size_t)ns);
         TD_HIP(ctx, hipMemcpyAsync(dq, h, sizeof(double) * 3 * (size_t)ns, hipMemcpyHostToDevice, s));
-        if (grid) {
-            const int nchunks = (int)((ns + kVolThreads - 1) / kVolThreads);
-            const int64_t blocks = (int64_t)kVolXcds * ((nmodels + kVolXcds - 1) / kVolXcds) * nchunks;
-            hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
-            if (ctx->vol_counting)
-                hipLaunchKernelGGL(k_vol_search<true>, dim3((unsigned)blocks), dim3(kVolThreads), 0, s, doff, dc, cs, dgrid,
-                                   dboff, dstart, dent, dq, (int)ns, (int)nmodels, nchunks, dv, dcount);
-            else
-                hipLaunchKernelGGL(k_vol_search<false>, dim3((unsigned)blocks), dim3(kVolThreads), 0, s, doff, dc, cs, dgrid,
-                                   dboff, dstart, dent, dq, (int)ns, (int)nmodels, nchunks, dv, dcount);
-            if (tm) tm->end("vol_search", t0, s);
-            TD_HIP(ctx, hipGetLastError());
-        } else {
-            TD_HIP(ctx, launch_raster_brute(doff, dc, cs, dq, (int)ns, (int)nmodels, dv, s, tm));
-            brute_pairs += nmodels * ns;
-        }
+        if (int rc = volume_sweep(ctx, S, 0, nmodels, dq, ns, dv)) return rc;
+        if (!grid) brute_pairs += nmodels * ns;
         TD_HIP(ctx, launch_raster_stats(dv, (int)nmodels, (int)ns, dm, dsd, s));
         TD_HIP(ctx, hipMemcpyAsync(vol->mean_out + q0, dm, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, s));
         TD_HIP(ctx, hipMemcpyAsync(vol->std_out + q0, dsd, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, s));

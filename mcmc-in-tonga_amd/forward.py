@@ -379,6 +379,78 @@ class TdContext:
 
         return self._volume(call, nm, qx, qy, qz, probs, bins, convergence, max_lag, want_values)
 
+    def set_predict_plan(self, slab_points=0, model_chunk=0):
+        """The ray points ``predict`` sweeps per slab and the models per sweep (0: auto).  Same answer."""
+        check(lib().tdt_set_predict_plan(self.h, int(slab_points), int(model_chunk)), self.h)
+
+    def set_predict_placement(self, xcd):
+        """Run the ray-sum workgroups of model m on XCD m % 8 (default: off).  Same answer."""
+        check(lib().tdt_set_predict_placement(self.h, int(bool(xcd))), self.h)
+
+    @staticmethod
+    def predict_plan(nmodels, ray_points, budget=0, forced_points=0, forced_chunk=0):
+        """(points per slab, models per sweep, the slabs' ray edges [slabs + 1]) of a ``predict`` call on
+        rays of ``ray_points`` points each (budget in bytes, 0: 1 GiB); needs no GPU."""
+        rp = np.ascontiguousarray(ray_points, dtype=np.int64).ravel()
+        out = np.zeros(3, dtype=np.int64)
+        edges = np.zeros(len(rp) + 1, dtype=np.int64)
+        check(lib().tdt_predict_plan(int(nmodels), len(rp), ptr(rp, _lib._pi64), int(budget), int(forced_points),
+                                     int(forced_chunk), ptr(out, _lib._pi64), ptr(edges, _lib._pi64)))
+        return int(out[0]), int(out[1]), [int(e) for e in edges[:int(out[2]) + 1]]
+
+    def _predict(self, call, nmodels, probs, bins, conv, max_lag, want_values):
+        """The td_predict request around ``call(byref(out))`` -> dict of the outputs."""
+        n = self.n
+        res = dict(phi=np.empty(nmodels), mean=np.empty(n), std=np.empty(n), quantiles=None, hist=None,
+                   ptS=np.empty((nmodels, n)) if want_values else None)
+        held = []
+        marg = cw = None
+        if len(np.ravel(probs)) or bins is not None:
+            marg, arrays, res["quantiles"], res["hist"] = self._marginals_want(n, probs, bins)
+            held.append(arrays)
+        if conv:
+            cw, arrays = self._convergence_want(n, max_lag, self.CONV_ALL)
+            res.update(arrays)
+        req = _lib.TdPredict(ptr(res["ptS"]), ptr(res["phi"]), ptr(res["mean"]), ptr(res["std"]),
+                             ctypes.addressof(marg) if marg is not None else None,
+                             ctypes.addressof(cw) if cw is not None else None)
+        call(ctypes.byref(req))
+        del held
+        return res
+
+    def predict(self, models, probs=(), bins=None, chain_len=None, max_lag=0, want_values=False):
+        """td_rasterize_predict: every model's predicted t* on THIS context's rays (which need not be the
+        rays the models were fitted to) in one sweep.  -> dict(phi[nmodels], the models' chi^2 against this
+        context's tS / allSig; mean[n], std[n] over the models per ray; quantiles[nprob, n] or None;
+        hist[n, nbins + 3] or None; with ``chain_len`` (the rows of each chain) rhat, ess, lags [n];
+        ptS[nmodels, n] or None).  Row k of ptS and phi[k] are ``evaluate`` of model k, bit for bit; the
+        statistics are ``rasterize`` / ``marginals`` / ``convergence`` of the matrix ptS.  models as for
+        ``rasterize``."""
+        off = np.zeros(len(models) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(m[0]) for m in models])
+        cat = [f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) if len(models) else np.zeros(0)
+               for k in range(4)]
+        lens = np.ascontiguousarray(chain_len, dtype=np.int64).ravel() if chain_len is not None else None
+
+        def call(req):
+            check(lib().td_rasterize_predict(self.h, len(models), ptr(off, _lib._pi64), *(ptr(c) for c in cat),
+                                             len(lens) if lens is not None else 0, ptr(lens, _lib._pi64), req), self.h)
+
+        return self._predict(call, len(models), probs, bins, lens is not None, max_lag, want_values)
+
+    def predict_history(self, histories, probs=(), bins=None, convergence=False, max_lag=0, want_values=False):
+        """td_history_predict: ``predict`` on the samples of the histories (chain.History) where they lie;
+        the histories may have been recorded on another context of this device.  With ``convergence`` one
+        history is one chain (one without samples is skipped)."""
+        histories = list(histories)
+        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
+        nm = sum(len(h) for h in histories)
+
+        def call(req):
+            check(lib().td_history_predict(self.h, hs, len(histories), req), self.h)
+
+        return self._predict(call, nm, probs, bins, convergence, max_lag, want_values)
+
     def interpolate(self, cells, X, Y, Z, want_nearest=False):
         """-> (zeta[npoints], nearest[npoints] or None)"""
         xc, yc, zc, ze = (f64(c) for c in cells)

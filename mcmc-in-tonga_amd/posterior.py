@@ -226,6 +226,51 @@ def posterior_volume(model_hist, dataStruct, TD_parameters, probs=(0.05, 0.5, 0.
     return out
 
 
+def posterior_predictive(model_hist, dataStruct, TD_parameters, probs=(0.05, 0.5, 0.95), bins=None, convergence=False,
+                         values=False, max_lag=0):
+    """Does the ensemble fit the data, ray by ray, and does it predict data it was not fitted to?  Every
+    model's forward t* on the rays of ``dataStruct`` -- which may differ from the one the ensemble was
+    sampled with: held-out rays, re-picked data, another allSig -- in one sweep on the device
+    (td_rasterize_predict / td_history_predict).  Same inputs as ``posterior_volume`` (Models, nested lists, a
+    ``History`` or a list of them, recorded on any context of the device).  -> dict: ``phi`` [nmodels], each
+    model's chi^2 against dataStruct.tS / allSig; ``mean``, ``std`` [n] of the predicted t* over the models;
+    ``quantiles`` [nprob, n]; ``hist`` [n, nbins + 3] with ``bins`` = (nbins, lo, hi); with ``convergence``
+    ``rhat``, ``ess``, ``lags`` [n] and ``summary`` as in ``convergence_maps``; with ``values`` ``ptS``
+    [nmodels, n]; ``residual`` = (mean - tS) / allSig; and, with at least two ``probs``, ``coverage``: the
+    share of rays whose observed tS lies within the outermost pair of quantiles."""
+    ctx = context_for(dataStruct)  # (TD_parameters: the siblings' signature)
+    models, lens = _chains(model_hist)
+    if _on_device(models):
+        r = ctx.predict_history(models, probs, bins, convergence, max_lag, values)
+    else:
+        r = ctx.predict([m.cells() for m in models], probs, bins, lens if convergence else None, max_lag, values)
+    tS = np.asarray(dataStruct.tS, dtype=np.float64).ravel()
+    sig = np.asarray(dataStruct.allSig, dtype=np.float64).ravel()
+    out = {"phi": r["phi"], "mean": r["mean"], "std": r["std"], "residual": (r["mean"] - tS) / sig}
+    q = r["quantiles"]
+    if q is not None:
+        out["quantiles"] = q
+        if len(q) >= 2:
+            lo, hi = q[int(np.argmin(np.ravel(probs)))], q[int(np.argmax(np.ravel(probs)))]
+            out["coverage"] = float(np.mean((tS >= lo) & (tS <= hi))) if len(tS) else float("nan")
+    if r["hist"] is not None:
+        out["hist"] = r["hist"]
+    if values:
+        out["ptS"] = r["ptS"]
+    if convergence:
+        rhat, ess = r["rhat"], r["ess"]
+        out.update(rhat=rhat, ess=ess, lags=r["lags"])
+        with np.errstate(invalid="ignore"):
+            out["summary"] = {
+                "rhat_max": float(np.nanmax(rhat)) if not np.all(np.isnan(rhat)) else float("nan"),
+                "ess_min": float(np.nanmin(ess)) if not np.all(np.isnan(ess)) else float("nan"),
+                "frac_rhat_above_1_01": float(np.mean(rhat > 1.01)),
+                "frac_capped": float(np.mean(r["lags"] < 0)),
+                "nan_columns": int(np.sum(np.isnan(rhat) | np.isnan(ess))),
+                "n": min(lens) // 2, "m": 2 * len(lens)}
+    return out
+
+
 def trace_diagnostics(histories, max_lag=0):
     """R-hat / ESS / lags of the two scalar traces of a ``History`` or a list of them (one chain each):
     {"phi": {rhat, ess, lags}, "ncells": {...}}, through td_convergence_values with two columns."""
