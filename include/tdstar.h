@@ -532,6 +532,60 @@ int td_rasterize_predict(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, 
 int td_history_predict(td_ctx *ctx, td_history *const *hs, int64_t nh, const td_predict *out);
 
 /* ------------------------------------------------------------------------
+ * Posterior covariance -- what trades off against what: the covariance and
+ * the correlation, over the models of an ensemble, between zeta at a few
+ * targets and zeta at every node of a lattice (or of any node list).  It is
+ * the ensemble's own point-spread function: when zeta at the target goes up
+ * across the samples, where does it go down, and how far does that reach.
+ *   td_rasterize_covariance takes td_rasterize's models, td_history_covariance
+ * the samples of the histories, history by history, where they lie (one
+ * without samples is skipped; a history need not belong to ctx, it must only
+ * live on ctx's device).  A lattice is sent x fastest.
+ *   Contract (M = the number of models).  v_q[k] is model k's nearest-cell
+ * zeta at node q, td_rasterize's value under td_rasterize's rules: the
+ * lexicographic minimum of (FP64 squared distance, cell index) below the 1e9
+ * sentinel, a NaN never wins, no answer gives 0.0.  a_t[k] is the series of
+ * target t: for a target point (tx, ty, tz) the nearest-cell value there, by
+ * the same sweep; else column t of series[M][nseries] (row = model: the
+ * layout of ptS_out and values_out, so a ray's predicted t*, the phi trace or
+ * the nCells trace can be handed in as it is).  m_q, s_q, m_t, s_t are
+ * td_rasterize's mean and sigma of those columns, from the same kernel
+ * (mean_out / std_out equal td_rasterize_volume's).  Then
+ *   cov[t][q]  = S / (M - 1), S = the sum over k of (v_q[k] - m_q)(a_t[k] - m_t)
+ * in td_rasterize's association (M < 16: left to right; else pairwise halves
+ * at mid = (lo + hi) >> 1 down to blocks of at most 1024, each block left to
+ * right), without FMA: each difference and each product is rounded once; and
+ *   corr[t][q] = cov[t][q] / (s_q * s_t), the product formed first, nothing
+ * clamped (a value 1 ulp beyond +-1 stays as it is).  M = 1 gives NaN, as
+ * sigma does; a zero sigma gives what the division gives; a NaN in a series
+ * gives a NaN row.  Output rows: the points first, then the series.
+ *   nq is 64-bit and no product with nmodels or nt + nseries is formed in 32
+ * bits; more than 2^25 models are TD_ERR_ARG.  The search structure and the
+ * slabs are the posterior volumes' (the value matrix never exists whole;
+ * tdt_set_volume_slab_nodes, _method and _counting are honoured) and the
+ * results depend on none of them.
+ *   TD_ERR_ARG, before any HIP call (the message, which names the entry
+ * point, through td_last_error(NULL) without a context), in this order: cov
+ * NULL; nq, nt or nseries < 0; nt + nseries == 0; cov_out and corr_out both
+ * NULL; a NULL coordinate array for a positive count; series NULL with
+ * nseries > 0; only one of mean_out / std_out or of tmean_out / tstd_out;
+ * offsets not monotone; no model or no sample in all; a history on another
+ * device; ctx NULL.  nq == 0 returns TD_OK (tmean_out / tstd_out are still
+ * written).  (csrc/covariance.hip)
+ * ------------------------------------------------------------------------ */
+typedef struct td_covariance {
+    const double *qx, *qy, *qz; int64_t nq;     /* any node list; a lattice is sent x fastest          */
+    const double *tx, *ty, *tz; int64_t nt;     /* target points, nullable when nt == 0                */
+    const double *series;       int64_t nseries;/* host [nmodels][nseries], nullable when nseries == 0 */
+    double *cov_out, *corr_out;                 /* [nt + nseries][nq]; each nullable, not both         */
+    double *mean_out, *std_out;                 /* [nq], nullable (both or neither)                    */
+    double *tmean_out, *tstd_out;               /* [nt + nseries], nullable (both or neither)          */
+} td_covariance;
+int td_rasterize_covariance(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const double *xCell,
+                            const double *yCell, const double *zCell, const double *zeta, const td_covariance *cov);
+int td_history_covariance(td_ctx *ctx, td_history *const *hs, int64_t nh, const td_covariance *cov);
+
+/* ------------------------------------------------------------------------
  * Resident tempering rounds (parallel tempering; the reference's
  * chains are independent pmap workers, main_inversion.jl:15, so this is a new
  * capability): DEVICE chains of one context run in ONE launch that stays

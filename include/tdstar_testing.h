@@ -251,6 +251,12 @@ int tdt_predict_plan(int64_t nmodels, int64_t n, const int64_t *ray_points, int6
 int tdt_set_predict_plan(td_ctx *ctx, int64_t slab_points, int64_t model_chunk);
 int tdt_set_predict_placement(td_ctx *ctx, int xcd);
 
+/* Posterior covariance (td_rasterize_covariance).  tdt_covariance_group: G, the targets k_cov_targets
+ * keeps in registers at a time (a slab's value matrix is read once per G targets; a target count that is
+ * no multiple of G gets a tail group); pure host code.  The volume hooks above (slab nodes, method,
+ * counting, counters) also act on and report a covariance call's sweeps. */
+int tdt_covariance_group(void);
+
 /* Diagnostic: the nearest-cell search alone, `reps` back-to-back launches over
  * the context's ray points on the given cells (method as tdt_set_nn_method,
  * 1..3), timed by two HIP events; *us_out = microseconds per search. */

@@ -68,6 +68,13 @@ class TdPredict(ctypes.Structure):
     _fields_ = [("ptS_out", _vp), ("phi_out", _vp), ("mean_out", _vp), ("std_out", _vp), ("marg", _vp), ("conv", _vp)]
 
 
+class TdCovariance(ctypes.Structure):
+    """td_covariance; the arrays as plain addresses (ptr())."""
+    _fields_ = [("qx", _vp), ("qy", _vp), ("qz", _vp), ("nq", _i64), ("tx", _vp), ("ty", _vp), ("tz", _vp), ("nt", _i64),
+                ("series", _vp), ("nseries", _i64), ("cov_out", _vp), ("corr_out", _vp), ("mean_out", _vp),
+                ("std_out", _vp), ("tmean_out", _vp), ("tstd_out", _vp)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/*.h
 SIGNATURES = {
     "td_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _pd, _pd, _pd, _pd, _pd, _i64, _i64, _pd, _pd]),
@@ -137,7 +144,10 @@ SIGNATURES = {
     "td_rasterize_predict": (ctypes.c_int, [_vp, _i64, _pi64, _pd, _pd, _pd, _pd, _i64, _pi64,
                                             ctypes.POINTER(TdPredict)]),
     "td_history_predict": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, ctypes.POINTER(TdPredict)]),
+    "td_rasterize_covariance": (ctypes.c_int, [_vp, _i64, _pi64, _pd, _pd, _pd, _pd, ctypes.POINTER(TdCovariance)]),
+    "td_history_covariance": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, ctypes.POINTER(TdCovariance)]),
     # include/tdstar_testing.h
+    "tdt_covariance_group": (ctypes.c_int, []),
     "tdt_predict_plan": (ctypes.c_int, [_i64, _i64, _pi64, _i64, _i64, _i64, _pi64, _pi64]),
     "tdt_set_predict_plan": (ctypes.c_int, [_vp, _i64, _i64]),
     "tdt_set_predict_placement": (ctypes.c_int, [_vp, ctypes.c_int]),

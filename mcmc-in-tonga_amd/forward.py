@@ -451,6 +451,75 @@ class TdContext:
 
         return self._predict(call, nm, probs, bins, convergence, max_lag, want_values)
 
+    @staticmethod
+    def covariance_group():
+        """G: the targets ``covariance`` keeps in registers at a time (a slab of the value matrix is read once
+        per G targets); needs no GPU."""
+        return int(lib().tdt_covariance_group())
+
+    def _covariance(self, call, nmodels, qx, qy, qz, targets, series, want):
+        """The td_covariance request around ``call(byref(req))`` -> dict of the outputs."""
+        qx, qy, qz = (f64(np.ravel(a)) for a in (qx, qy, qz))
+        nq = len(qx)
+        if not (len(qy) == len(qz) == nq):
+            raise ValueError("qx, qy and qz must have the same length")
+        tg = f64(np.reshape(targets, (-1, 3)).T) if targets is not None else np.zeros((3, 0))  # [3][nt]
+        nt = tg.shape[1]
+        ser = None
+        if series is not None:
+            ser = f64(series)
+            if ser.ndim == 1:
+                ser = ser.reshape(-1, 1)
+            if ser.ndim != 2 or ser.shape[0] != nmodels:
+                raise ValueError("series must be [nmodels = %d][nseries], row = model; got %s" % (nmodels, ser.shape))
+            if ser.shape[1] == 0:
+                ser = None
+        nser = ser.shape[1] if ser is not None else 0
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not set(want) <= {"cov", "corr"}:
+            raise ValueError("want: 'cov' and / or 'corr'")
+        T = nt + nser
+        res = dict(cov=np.empty((T, nq)) if "cov" in want else None, corr=np.empty((T, nq)) if "corr" in want else None,
+                   mean=np.empty(nq), std=np.empty(nq), target_mean=np.empty(T), target_std=np.empty(T))
+        req = _lib.TdCovariance(ptr(qx), ptr(qy), ptr(qz), nq, ptr(tg[0]) if nt else None, ptr(tg[1]) if nt else None,
+                                ptr(tg[2]) if nt else None, nt, ptr(ser), nser, ptr(res["cov"]), ptr(res["corr"]),
+                                ptr(res["mean"]), ptr(res["std"]), ptr(res["target_mean"]), ptr(res["target_std"]))
+        call(ctypes.byref(req))
+        return res
+
+    def covariance(self, models, qx, qy, qz, targets=None, series=None, want=("cov", "corr")):
+        """td_rasterize_covariance: the covariance and the correlation, over the models, between zeta at each
+        target and zeta at every node -- the ensemble's point-spread function.  ``targets``: points [nt, 3]
+        (x, y, z), whose series is the nearest-cell value there; ``series``: [nmodels, nseries] (row = model),
+        any per-model numbers (a ray's predicted t* out of ``predict``, the phi trace, ...).  -> dict(cov[T, nq],
+        corr[T, nq] (each None unless in ``want``), mean[nq], std[nq] (``volume``'s), target_mean[T],
+        target_std[T]); rows: the points, then the series.  cov = sum((v - mean)(a - target_mean)) / (M - 1) in
+        ``rasterize``'s association without FMA, corr = cov / (std * target_std), unclamped.  Any number of
+        nodes, swept slab by slab as by ``volume``.  models as for ``rasterize``."""
+        off = np.zeros(len(models) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(m[0]) for m in models])
+        cat = [f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) if len(models) else np.zeros(0)
+               for k in range(4)]
+
+        def call(req):
+            check(lib().td_rasterize_covariance(self.h, len(models), ptr(off, _lib._pi64), *(ptr(c) for c in cat), req),
+                  self.h)
+
+        return self._covariance(call, len(models), qx, qy, qz, targets, series, want)
+
+    def covariance_history(self, histories, qx, qy, qz, targets=None, series=None, want=("cov", "corr")):
+        """td_history_covariance: ``covariance`` on the samples of the histories (chain.History) where they
+        lie, history by history (one without samples is skipped); they may have been recorded on another
+        context of this device."""
+        histories = list(histories)
+        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
+        nm = sum(len(h) for h in histories)
+
+        def call(req):
+            check(lib().td_history_covariance(self.h, hs, len(histories), req), self.h)
+
+        return self._covariance(call, nm, qx, qy, qz, targets, series, want)
+
     def interpolate(self, cells, X, Y, Z, want_nearest=False):
         """-> (zeta[npoints], nearest[npoints] or None)"""
         xc, yc, zc, ze = (f64(c) for c in cells)

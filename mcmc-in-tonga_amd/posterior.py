@@ -226,6 +226,40 @@ def posterior_volume(model_hist, dataStruct, TD_parameters, probs=(0.05, 0.5, 0.
     return out
 
 
+def posterior_covariance(model_hist, dataStruct, TD_parameters, targets, series=None, xs=None, ys=None, zs=None):
+    """What trades off against what: the covariance and the correlation, over the models, between zeta at each
+    target and zeta at every node of the lattice ``xs`` x ``ys`` x ``zs`` (default: dataStruct.xVec / yVec /
+    zVec) -- the ensemble's own point-spread function, the Bayesian stand-in for a checkerboard test.
+    ``targets``: points [nt, 3] (x, y, z; None for none); ``series``: [nmodels, nseries] per-model numbers
+    (row = model: a ray's predicted t* out of ``posterior_predictive(values=True)["ptS"]``, the phi trace,
+    ...).  Same inputs as ``posterior_volume`` (Models, nested lists, a ``History`` or a list of them).
+    -> dict: ``cov``, ``corr`` [T, nx, ny, nz] (rows: the points, then the series), ``mean``, ``std`` [nx, ny,
+    nz] (``posterior_volume``'s), ``target_mean``, ``target_std`` [T], ``node_volume`` (the product of the
+    lattice's mean spacings, km^3; an axis of one node counts 1), ``footprint`` [T]: the nodes with corr >=
+    0.5 times node_volume, and ``x``, ``y``, ``z``.  Computed on the device slab by slab
+    (td_rasterize_covariance / td_history_covariance)."""
+    ctx = context_for(dataStruct)  # (TD_parameters: the siblings' signature; the lattice decides everything here)
+    xv, yv, zv = (np.asarray(v if v is not None else d, dtype=np.float64).ravel()
+                  for v, d in ((xs, dataStruct.xVec), (ys, dataStruct.yVec), (zs, dataStruct.zVec)))
+    shape = (len(zv), len(yv), len(xv))  # x fastest
+    qx = np.tile(xv, len(yv) * len(zv))
+    qy = np.tile(np.repeat(yv, len(xv)), len(zv))
+    qz = np.repeat(zv, len(xv) * len(yv))
+    models, _ = _chains(model_hist)
+    if _on_device(models):
+        r = ctx.covariance_history(models, qx, qy, qz, targets, series)
+    else:
+        r = ctx.covariance([m.cells() for m in models], qx, qy, qz, targets, series)
+    out = {"x": xv, "y": yv, "z": zv, "target_mean": r["target_mean"], "target_std": r["target_std"]}
+    for f in ("mean", "std"):
+        out[f] = r[f].reshape(shape).transpose(2, 1, 0).copy()
+    for f in ("cov", "corr"):
+        out[f] = r[f].reshape((len(r[f]),) + shape).transpose(0, 3, 2, 1).copy()
+    out["node_volume"] = float(np.prod([(v[-1] - v[0]) / (len(v) - 1) for v in (xv, yv, zv) if len(v) > 1]))
+    out["footprint"] = np.sum(r["corr"] >= 0.5, axis=1) * out["node_volume"]
+    return out
+
+
 def posterior_predictive(model_hist, dataStruct, TD_parameters, probs=(0.05, 0.5, 0.95), bins=None, convergence=False,
                          values=False, max_lag=0):
     """Does the ensemble fit the data, ray by ray, and does it predict data it was not fitted to?  Every
