@@ -124,6 +124,17 @@ int tdt_host_nn_query(const double *x, const double *y, const double *z, const d
                       const double *edits, int64_t nedits, const double *pending, const double *qx,
                       const double *qy, const double *qz, int64_t nq, double *val_out, int64_t *pos_out);
 
+/* Testing: the bucket grid's lower bound on the host (csrc/internal.h grid_axis / grid_block_lb, the code
+ * the evaluate grid, the chain's grid query and the volume sweep prove their answers with).  Makes the
+ * grid of make_cell_grid(lo, hi, target, max_dim, max_buckets) and, for each of npts points, writes its
+ * bucket ijk[3 p .. 3 p + 2] = (i, j, k) and lb[p] = grid_block_lb(G, x, y, z, R): a strict lower bound
+ * of the FP64 squared distance to every cell whose bucket lies outside the point's (2R+1)^3 block.
+ * dims, h, e (each nullable, 3 entries): the grid's buckets, bucket edges and face allowances per axis.
+ * Host only. */
+int tdt_grid_lb(const double lo[3], const double hi[3], double target, int max_dim, int64_t max_buckets,
+                const double *px, const double *py, const double *pz, int64_t npts, int R, int32_t *ijk, double *lb,
+                int32_t dims[3], double h[3], double e[3]);
+
 /* Diagnostic: the drop-in path's wall time per stage, ns, accumulated on the
  * context (then zeroed if reset): [0] td_evaluate, [1] its model
  * classification (which state the caller's cells are an edit of), [2] its

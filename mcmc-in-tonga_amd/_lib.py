@@ -194,6 +194,8 @@ SIGNATURES = {
     "tdt_rounds_force_exit": (ctypes.c_int, [_vp, _pi32, _i64]),
     "tdt_dropin_timing": (ctypes.c_int, [_vp, ctypes.c_int, _pi64]),
     "tdt_host_nn_query": (ctypes.c_int, [_pd, _pd, _pd, _pd, _i64, _pd, _i64, _pd, _pd, _pd, _pd, _i64, _pd, _pi64]),
+    "tdt_grid_lb": (ctypes.c_int, [_pd, _pd, _d, ctypes.c_int, _i64, _pd, _pd, _pd, _i64, ctypes.c_int, _pi32, _pd,
+                                   _pi32, _pd, _pd]),
     "tdt_shadow_diag": (ctypes.c_int, [_vp, _pi64]),
     "tdt_shadow_profile": (ctypes.c_int, [_vp, _pi64]),
     "tdt_chi2": (ctypes.c_int, [_vp, _pd, ctypes.c_int, _pd]),

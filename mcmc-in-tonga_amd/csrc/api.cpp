@@ -130,6 +130,27 @@ CellGrid make_cell_grid(const double lo[3], const double hi[3], double target, i
     return G;
 }
 
+// Testing (include/tdstar_testing.h): make_cell_grid on a caller's box, then every point's bucket and
+// grid_block_lb -- the host instance of the code the kernels run.  Host only.
+extern "C" int tdt_grid_lb(const double lo[3], const double hi[3], double target, int max_dim, int64_t max_buckets,
+                           const double *px, const double *py, const double *pz, int64_t npts, int R, int32_t *ijk,
+                           double *lb, int32_t dims[3], double h[3], double e[3]) {
+    if (!lo || !hi || npts < 0 || (npts > 0 && (!px || !py || !pz || !ijk || !lb)) || R < 0 || max_dim < 1 ||
+        max_buckets < 1)
+        return set_err(nullptr, TD_ERR_ARG, "tdt_grid_lb: bad argument");
+    const CellGrid G = make_cell_grid(lo, hi, target, max_dim, max_buckets);
+    if (dims) { dims[0] = G.gx; dims[1] = G.gy; dims[2] = G.gz; }
+    if (h) { h[0] = G.hx; h[1] = G.hy; h[2] = G.hz; }
+    if (e) { e[0] = G.ex; e[1] = G.ey; e[2] = G.ez; }
+    for (int64_t p = 0; p < npts; ++p) {
+        ijk[3 * p + 0] = grid_axis(px[p], G.x0, G.ix, G.gx);
+        ijk[3 * p + 1] = grid_axis(py[p], G.y0, G.iy, G.gy);
+        ijk[3 * p + 2] = grid_axis(pz[p], G.z0, G.iz, G.gz);
+        lb[p] = grid_block_lb(G, px[p], py[p], pz[p], R);
+    }
+    return TD_OK;
+}
+
 int ensure_cells(td_ctx *ctx, int64_t ncells) {
     if (ncells <= ctx->cell_cap && ctx->cells) return TD_OK;
     int64_t cap = ctx->cell_cap > 0 ? ctx->cell_cap : 256;
