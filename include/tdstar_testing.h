@@ -57,6 +57,10 @@ int tdt_chain_variant_rounds(const int64_t in[15], int rounds_rec, int64_t out[8
 /* Launches of each k_chain_run instance by this process since it started: out[i] for table position i,
  * *n = the table's length (out has room for 32).  Host only. */
 int tdt_chain_launch_counts(int64_t out[32], int *n);
+/* Launches of k_draws (the draws of a whole launch precomputed ahead of k_chain_run) by this process since it
+ * started.  A launch that draws inside the kernel instead -- a resident or round launch, one whose draws
+ * would exceed the budget, every launch under TD_PRE_DRAWS=0 -- adds none.  Host only. */
+int tdt_chain_draws_launches(int64_t *n);
 /* The pack kernel of a recorded ladder (csrc/history_pack.hip) on caller-given slots: cells = host [4][stride]
  * (x, y, z, zeta rows), `count` slots of slot_cells cells from cell slot0 of every row, ncells[count] the cells
  * each slot holds (0 .. slot_cells).  On return the samples lie packed from slot0 on in every row (the cells

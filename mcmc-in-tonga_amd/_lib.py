@@ -173,6 +173,7 @@ SIGNATURES = {
     "tdt_chain_variant": (ctypes.c_int, [_pi64, _pi64]),
     "tdt_chain_variant_rounds": (ctypes.c_int, [_pi64, ctypes.c_int, _pi64]),
     "tdt_chain_launch_counts": (ctypes.c_int, [_pi64, ctypes.POINTER(ctypes.c_int)]),
+    "tdt_chain_draws_launches": (ctypes.c_int, [_pi64]),
     "tdt_history_pack": (ctypes.c_int, [ctypes.c_int, _pd, _i64, _i64, _i64, _pi32, _i64, _pi64]),
     "tdt_history_pack_chunk": (ctypes.c_int, []),
     "tdt_chain_query_lat": (ctypes.c_int, [_vp, _pd, ctypes.c_int, ctypes.c_int, _pi64]),

@@ -866,6 +866,12 @@ int tdt_chain_launch_counts(int64_t out[32], int *n) {
     return TD_OK;
 }
 
+int tdt_chain_draws_launches(int64_t *n) {
+    if (!n) return TD_ERR_ARG;
+    *n = chain_draws_launches();
+    return TD_OK;
+}
+
 int tdt_set_nn_method(td_ctx *ctx, int method) {
     if (!ctx || method < 0 || method > 3) return TD_ERR_ARG;
     ctx->nn_method = method == 3 ? 1 : method;  // 3: brute force through the split search

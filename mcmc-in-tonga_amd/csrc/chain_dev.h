@@ -309,6 +309,8 @@ int chain_variant_index(const ChainVariant &v);
 // chain_run's launches of each table entry by this process: out[i] for i < min(cap, the table's length), which
 // it returns (host only)
 int chain_launch_counts(int64_t *out, int cap);
+// chain_run's launches of k_draws by this process (host only): none for a launch that draws inside the kernel
+int64_t chain_draws_launches();
 // Testing: the chain's chi^2 code on a caller-given ptS (n <= 4096) --
 // path 2: k_chi2_prefix (the starting state's sequential prefix sums, what
 // chain_full_state runs), 3: the proposal-time sum (the terms of MCsub.jl:171,

@@ -2018,6 +2018,12 @@ int chain_launch_counts(int64_t *out, int cap) {
     return n;
 }
 
+// ... and of k_draws (host only; testing: a launch that means to draw inside the kernel can tell that no
+// draws were precomputed for it, tdt_chain_draws_launches)
+static std::atomic<int64_t> g_draws_launches;
+
+int64_t chain_draws_launches() { return g_draws_launches.load(std::memory_order_relaxed); }
+
 hipError_t chain_run(const DevChain *host, const DevChain *dev, int nchains, int64_t iters, hipStream_t s,
                      const ScriptArgs *script, DrawsBuf db, int num_cus) {
     ScriptArgs sa{};
@@ -2044,6 +2050,7 @@ hipError_t chain_run(const DevChain *host, const DevChain *dev, int nchains, int
             if (e != hipSuccess) return e;
             *db.bytes = pre_bytes;
         }
+        g_draws_launches.fetch_add(1, std::memory_order_relaxed);
         hipLaunchKernelGGL(k_draws, dim3((unsigned)((iters + 255) / 256), (unsigned)nchains), dim3(256), 0, s, dev,
                            (long long)iters, static_cast<tdchain::Draws *>(*db.p));
         sa.pre = static_cast<const tdchain::Draws *>(*db.p);

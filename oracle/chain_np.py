@@ -27,10 +27,13 @@ import math
 import numpy as np
 
 
-def run(K, iters, box, prior=1, seed=0, sig=10, zeta_scale=50, max_cells=100, min_cells=5):
+def run(K, iters, box, prior=1, seed=0, sig=10, zeta_scale=50, max_cells=100, min_cells=5, rng=None, start=None):
     """K independent prior-sampling chains, `iters` iterations each.
-    Returns (nCells[K], zeta list of arrays, x list of arrays)."""
-    rng = np.random.default_rng(seed)
+    Returns (nCells[K], zeta list of arrays, x list of arrays).
+    `rng` (testing: tests/test_chain_reference.py feeds this loop and oracle/chain_ref.py the same numbers):
+    what draws instead of default_rng(seed) -- integers, random, standard_normal, normal as numpy's Generator
+    has them; `start`: every chain's starting cells (x, y, z, zeta) instead of build_starting's."""
+    rng = np.random.default_rng(seed) if rng is None else rng
     xmin, xmax, ymin, ymax, zmin, zmax = box
     lo = np.array([xmin, ymin, zmin])
     hi = np.array([xmax, ymax, zmax])
@@ -42,8 +45,13 @@ def run(K, iters, box, prior=1, seed=0, sig=10, zeta_scale=50, max_cells=100, mi
     C = np.full((K, M, 3), np.nan)
     Z = np.zeros((K, M))
     # build_starting (MCsub.jl:86-108)
-    N = np.floor(np.exp(rng.random(K) * math.log(max_cells / min_cells) + math.log(min_cells))).astype(np.int64)
-    for k in range(K):
+    if start is not None:
+        N = np.full(K, len(start[0]), dtype=np.int64)
+        C[:, :N[0]] = np.stack([np.asarray(a, dtype=np.float64) for a in start[:3]], 1)
+        Z[:, :N[0]] = start[3]
+    else:
+        N = np.floor(np.exp(rng.random(K) * math.log(max_cells / min_cells) + math.log(min_cells))).astype(np.int64)
+    for k in range(K if start is None else 0):
         n = N[k]
         C[k, :n] = lo + (hi - lo) * rng.random((n, 3))
         if prior == 1:
