@@ -111,6 +111,13 @@ int tdt_chain_set_exact_every(td_chain *ch, int k);
  * idle watchdog can fire first (the race of a descheduled host thread).  The
  * command must then be re-issued to a new launch with the same results.  0 = off. */
 int tdt_set_server_post_delay(int ms);
+/* The resident launches registered to the calling thread: td_evaluate's shadow servers and the launches of
+ * td_rounds_*, i.e. what "the library stops this thread's resident kernels" (include/tdstar.h,
+ * td_set_incremental) would stop.  0 on return from every entry point that issues other GPU work; 1 after
+ * the calls documented to keep their server (td_evaluate's incremental path, the one-point td_interpolate,
+ * a DROPIN chain's run) and after a round of td_rounds_run / _temper.  A launch that returned by its own
+ * idle watchdog stays registered until the next call notices.  Host only. */
+int tdt_resident_count(int64_t *n);
 /* Resident tempering rounds (td_rounds_*): at the next launch the workgroups of
  * the listed chains return at their first wait, before the host posts the
  * round, while the others run it -- the race of a workgroup's idle watchdog

@@ -192,6 +192,7 @@ SIGNATURES = {
     "tdt_wave_seq_sum": (ctypes.c_int, [ctypes.c_int, _pd, _i64, _d, _pd, _pd, _pi32]),
     "tdt_set_incremental": (ctypes.c_int, [_vp, ctypes.c_int]),
     "tdt_set_server_post_delay": (ctypes.c_int, [ctypes.c_int]),
+    "tdt_resident_count": (ctypes.c_int, [_pi64]),
     "tdt_rounds_force_exit": (ctypes.c_int, [_vp, _pi32, _i64]),
     "tdt_dropin_timing": (ctypes.c_int, [_vp, ctypes.c_int, _pi64]),
     "tdt_host_nn_query": (ctypes.c_int, [_pd, _pd, _pd, _pd, _i64, _pd, _i64, _pd, _pd, _pd, _pd, _i64, _pd, _pi64]),

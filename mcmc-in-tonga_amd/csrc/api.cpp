@@ -585,11 +585,14 @@ int td_evaluate_batch(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, con
                       double *phi_out, double *likelihood_out) {
     if (!ctx) return set_err(nullptr, TD_ERR_ARG, "td_evaluate_batch: ctx is NULL");
     if (nmodels < 0 || (nmodels > 0 && !cell_off)) return set_err(ctx, TD_ERR_ARG, "td_evaluate_batch: bad offsets");
-    for (int64_t k = 0; k < nmodels; ++k) {
+    for (int64_t k = 0; k < nmodels; ++k) {  // (every check before the first model is evaluated)
         const int64_t a = cell_off[k], b = cell_off[k + 1];
         if (b < a || a < 0) return set_err(ctx, TD_ERR_ARG, "td_evaluate_batch: offsets not monotone");
         if (b > a && (!xCell || !yCell || !zCell || !zeta))
             return set_err(ctx, TD_ERR_ARG, "td_evaluate_batch: bad cell arrays");
+    }
+    for (int64_t k = 0; k < nmodels; ++k) {
+        const int64_t a = cell_off[k], b = cell_off[k + 1];
         TD_HIP(ctx, hipSetDevice(ctx->device));
         servers_quiesce(nullptr);
         // independent models: the full evaluate (no shadow chain)

@@ -607,6 +607,17 @@ void servers_quiesce(const td_chain *keep) {
 }
 }  // namespace tdstar
 
+// testing hook: the resident launches (shadow servers and tempering rounds) registered to the calling
+// thread -- what servers_quiesce(nullptr) would stop.  Host only.
+extern "C" int tdt_resident_count(int64_t *n) {
+    if (!n) return TD_ERR_ARG;
+    std::lock_guard<std::mutex> g(g_res_mu);
+    int64_t k = 0;
+    for (const Resident &e : g_res) k += e.owner == std::this_thread::get_id();
+    *n = k;
+    return TD_OK;
+}
+
 namespace {
 
 void free_chain(td_chain *ch) {

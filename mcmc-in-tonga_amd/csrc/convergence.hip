@@ -363,6 +363,7 @@ extern "C" int td_convergence_values(td_ctx *ctx, const double *values, int64_t 
     if (ncol > INT32_MAX || (uint64_t)M > (uint64_t)INT64_MAX / 8 / (uint64_t)ncol)
         return set_err(ctx, TD_ERR_ARG, std::string(who) + ": too large");
     TD_HIP(ctx, hipSetDevice(ctx->device));
+    servers_quiesce(nullptr);
     const size_t nv = (size_t)M * (size_t)ncol;
     if (int rc = raster_reserve(ctx, nv, nv)) return rc;
     TD_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the staging block may still feed a previous copy

@@ -115,6 +115,7 @@ int td_history_create(td_history **out, td_ctx *ctx, int64_t max_samples, int64_
                          padded(S * sizeof(long long)) + padded(S * sizeof(double)) + 3 * padded(S * sizeof(int)) +
                          (pts ? padded(S * (size_t)n * sizeof(double)) : 0);
     hipError_t e = hipSetDevice(ctx->device);
+    servers_quiesce(nullptr);  // (the allocation and the memset below wait for the device)
     if (e == hipSuccess) e = hipMalloc(&h->block, bytes);
     if (e != hipSuccess) {
         delete h;
@@ -179,6 +180,7 @@ int td_history_read(td_history *h, int64_t first, int64_t count, int64_t *off_ou
         return set_err(c, TD_ERR_ARG, "td_history_read: cell_cap smaller than the samples' cells");
     if (count == 0) return TD_OK;
     TD_HIP(c, hipSetDevice(c->device));
+    servers_quiesce(nullptr);
     double *dst[4] = {x, y, z, zeta};
     for (int comp = 0; comp < 4; ++comp)
         if (dst[comp] && ncell > 0)
@@ -211,6 +213,7 @@ int tdt_history_pack(int device, double *cells, int64_t stride, int64_t slot0, i
     off_out[0] = slot0;
     if (count == 0) return TD_OK;
     if (device >= 0) TD_HIP(nullptr, hipSetDevice(device));
+    servers_quiesce(nullptr);
     const size_t cb = sizeof(double) * 4 * (size_t)stride, nb = sizeof(int) * (size_t)count,
                  ob = sizeof(long long) * (size_t)(count + 1);
     double *d_cells = nullptr;

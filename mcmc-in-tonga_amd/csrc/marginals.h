@@ -31,6 +31,11 @@ __host__ __device__ inline int marg_slot(double v, double lo, double hi, double 
 int marg_check_want(td_ctx *ctx, const td_marginals *want, const char *who);
 int marg_check_bins(td_ctx *ctx, int64_t nbins, double lo, double hi, const char *who);
 
+// The one refusal that depends on the number of models M (the resident regime forced on a column it
+// cannot hold), for the entry points to make before they issue anything: marginals_run itself runs
+// behind their search kernels and copies.  want may be NULL.
+int marg_check_models(td_ctx *ctx, const td_marginals *want, int64_t M);
+
 // Quantiles and histograms of the device value matrix values[M][nq] (left unchanged), enqueued on
 // ctx->stream with the copies to want's host arrays; the caller synchronises.
 int marginals_run(td_ctx *ctx, const double *values, int64_t M, int64_t nq, const td_marginals *want);

@@ -235,13 +235,18 @@ int marg_check_want(td_ctx *ctx, const td_marginals *want, const char *who) {
     return TD_OK;
 }
 
+int marg_check_models(td_ctx *ctx, const td_marginals *want, int64_t M) {
+    if (want && (want->nprob > 0 || want->nbins > 0) && ctx->marg_method == 1 && M > kMargResidentMax)
+        return set_err(ctx, TD_ERR_ARG, "td_marginals: the resident regime cannot hold this many models");
+    return TD_OK;
+}
+
 int marginals_run(td_ctx *ctx, const double *values, int64_t M, int64_t nq, const td_marginals *want) {
     const int nprob = (int)want->nprob, nbins = (int)want->nbins;
     if (nq == 0 || (nprob == 0 && nbins == 0)) return TD_OK;
     const int64_t slots = nbins + 3;
     if (nbins > 0 && nq > INT64_C(0x7fffffff) / slots) return set_err(ctx, TD_ERR_ARG, "td_marginals: nq * (nbins + 3) too large");
-    if (ctx->marg_method == 1 && M > kMargResidentMax)
-        return set_err(ctx, TD_ERR_ARG, "td_marginals: the resident regime cannot hold this many models");
+    if (int rc = marg_check_models(ctx, want, M)) return rc;  // (the entry points have made it already)
     const size_t par_b = sizeof(QuantPar), quant_b = sizeof(double) * (size_t)nprob * nq,
                  hist_b = nbins > 0 ? sizeof(int64_t) * (size_t)nq * slots : 0;
     if (int rc = ensure_marg(ctx, par_b + quant_b + hist_b)) return rc;
@@ -321,6 +326,7 @@ extern "C" int td_history_zeta_hist(td_ctx *ctx, td_history *const *hs, int64_t 
     const double w = (hi - lo) / (double)nbins;
     const size_t hist_b = sizeof(int64_t) * (size_t)(nbins + 3);
     TD_HIP(ctx, hipSetDevice(ctx->device));
+    servers_quiesce(nullptr);
     if (int rc = ensure_marg(ctx, hist_b)) return rc;
     unsigned long long *dhist = static_cast<unsigned long long *>(ctx->marg);
     TD_HIP(ctx, hipMemsetAsync(dhist, 0, hist_b, ctx->stream));

@@ -168,6 +168,7 @@ int predict_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *c
         if (out->phi_out) std::fill(out->phi_out, out->phi_out + nmodels, 0.0);
         return TD_OK;
     }
+    if (int rc = marg_check_models(ctx, out->marg, nmodels)) return rc;  // (before anything is issued)
     TD_HIP(ctx, hipSetDevice(ctx->device));
     servers_quiesce(nullptr);
     VolSearch S;

@@ -289,7 +289,11 @@ int rasterize_core(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const 
     if (nq == 0) return TD_OK;
     if (nq > 0x7fffffff / std::max<int64_t>(nmodels, 1) || total > 0x7fffffff)
         return set_err(ctx, TD_ERR_ARG, "td_rasterize: too large");
+    // marginals_run's own refusal, made here before anything is issued: there the search kernels and the
+    // copies into mean_out / std_out are already under way, and the call would return while they run
+    if (int rc = marg_check_models(ctx, want, nmodels)) return rc;
     TD_HIP(ctx, hipSetDevice(ctx->device));
+    servers_quiesce(nullptr);
     // one device block: queries (3 nq), all cells SoA (4 total), values (nmodels nq), mean, std (2 nq)
     const size_t nd = 3 * (size_t)nq + 4 * (size_t)std::max<int64_t>(total, 1) + (size_t)nmodels * nq + 2 * (size_t)nq;
     const int64_t cs = std::max<int64_t>(total, 1);  // SoA stride of the cells

@@ -294,6 +294,7 @@ int volume_build(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *c
     for (int64_t k = 0; k < nmodels; ++k)
         if (cell_off[k + 1] - cell_off[k] > INT32_MAX) return set_err(ctx, TD_ERR_ARG, w + ": a model of too many cells");
     TD_HIP(ctx, hipSetDevice(ctx->device));
+    servers_quiesce(nullptr);  // (both volume entry points; the predictive and covariance calls have stopped them already)
     hipStream_t s = ctx->stream;
     Timer *tm = ctx->timer.on ? &ctx->timer : nullptr;
     const bool grid = ctx->vol_method == 1 || (ctx->vol_method == 0 && total / nmodels >= kVolGridMinMeanCells);
@@ -404,6 +405,7 @@ namespace {
 int volume_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *cell_off, const double *xCell,
                 const double *yCell, const double *zCell, const double *zeta, const std::vector<td_history *> *segs,
                 int64_t nchains, const int64_t *chain_len, const td_volume *vol) {
+    if (int rc = marg_check_models(ctx, vol->marg, nmodels)) return rc;  // (before anything is issued)
     VolSearch S;
     if (int rc = volume_build(ctx, who, nmodels, cell_off, xCell, yCell, zCell, zeta, segs, &S)) return rc;
     const int64_t nq = vol->nq;
