@@ -35,14 +35,21 @@ int tdt_propose(const td_chain_params *prm, uint64_t iter, int64_t ncells, const
  * move), [12..13] commit / next proposal, [14] proven early rejections, [15]
  * grid searches that fell back to a full scan, [16 + 10 (action-1) + j] the
  * phases split by action (j: A..F, commit, next proposal, final barrier),
- * [56 + w] phase F of wave w, [64] chi^2 tail terms, [65] chi^2 scan rounds.
- * Never enabled in measured runs. */
+ * [56 + w] phase F of wave w, [64] chi^2 tail terms, [65] chi^2 scan rounds;
+ * [35] / [45] deaths / changes taken on the short road (the cell owned no ray
+ * point), [55] guessed proposals adopted with the barren flag up, [25] those
+ * whose flag was cleared at adoption.  Never enabled in measured runs. */
 int tdt_chain_profile(td_chain *ch, int enable, int64_t out[80]);
 /* LDS plan of a device chain: [0] bytes of the LDS layout (tiles, rays and
  * order mirrored), [1] bytes of the HBM layout, [2] 1 if the HBM layout holds
  * its super-tiles in LDS, [3] 1 if a free-running launch of this chain alone
  * takes the LDS layout (it fits and the chain's lds_mode is 0). */
 int tdt_chain_lds(td_chain *ch, int64_t out[4]);
+/* The DEVICE engine's per-slot point counts (csrc/chain_dev.h DevChain::own) against a recount of the cached
+ * nearest slots: both arrays are copied back, and the number of slots whose count differs (plus the points
+ * with no valid owner) is returned -- 0 when the invariant own[s] == #{q : best_s[q] == s} holds.  A negative
+ * value is minus a td_status.  Needs a GPU. */
+int tdt_chain_own_check(td_chain *ch);
 /* The k_chain_run instance and dynamic LDS size a launch takes (csrc/chain_variant.h; host only, no
  * context).  in: [0..3] the chains' largest LDS plans small, big, half, hyb; [4..7] force_hbm, packed,
  * tiles_ok, all_auto (over the chains' lds_mode); [8] scripted, [9] some chain records, [10] exchange

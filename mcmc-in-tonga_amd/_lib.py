@@ -170,6 +170,7 @@ SIGNATURES = {
     "tdt_propose": (ctypes.c_int, [ctypes.POINTER(TdChainParams), _u64, _i64, _pd, _pd, _pd, _pd, _d, _pd]),
     "tdt_chain_profile": (ctypes.c_int, [_vp, ctypes.c_int, _pi64]),
     "tdt_chain_lds": (ctypes.c_int, [_vp, _pi64]),
+    "tdt_chain_own_check": (ctypes.c_int, [_vp]),
     "tdt_chain_variant": (ctypes.c_int, [_pi64, _pi64]),
     "tdt_chain_variant_rounds": (ctypes.c_int, [_pi64, ctypes.c_int, _pi64]),
     "tdt_chain_launch_counts": (ctypes.c_int, [_pi64, ctypes.POINTER(ctypes.c_int)]),

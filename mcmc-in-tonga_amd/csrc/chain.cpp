@@ -413,7 +413,7 @@ int device_setup(td_chain *ch) {
     add(sizeof(float) * 3 * ntiles); add(sizeof(float) * 3 * ntiles); add(sizeof(double) * (ntiles + 1)); add(sizeof(double) * (ntiles + 1));
     add(sizeof(float) * 3 * std::max(nsuper, 1)); add(sizeof(float) * 3 * std::max(nsuper, 1));
     add(sizeof(double) * 4 * cap); add(sizeof(double) * (cap + 2)); for (int i = 0; i < 3; ++i) add(sizeof(int) * cap); add(sizeof(long long) * cap);
-    add(sizeof(int) * Pn); add(sizeof(double) * Pn); add(sizeof(double) * Pn);
+    add(sizeof(int) * Pn); add(sizeof(double) * Pn); add(sizeof(double) * Pn); add(sizeof(int) * cap);
     add(sizeof(int) * Pn); add(sizeof(double) * Pn); add(sizeof(double) * Pn); add(Pn);
     add(sizeof(int) * Pn); add(sizeof(int) * Pn); add(sizeof(int) * (ntiles + 1));
     for (int i = 0; i < 6; ++i) add(sizeof(double) * nn);
@@ -450,6 +450,7 @@ int device_setup(td_chain *ch) {
     d.free_slots = carve<int>(cur, cap); d.order_tmp = carve<int>(cur, cap);
     d.cap = cap;
     d.best_s = carve<int>(cur, Pn); d.best_d = carve<double>(cur, Pn); d.zeta0 = carve<double>(cur, Pn);
+    d.own = carve<int>(cur, cap);  // (zero from the memset above; chain_full_state counts it)
     d.cand_s = carve<int>(cur, Pn); d.cand_d = carve<double>(cur, Pn); d.cand_z = carve<double>(cur, Pn);
     d.cand_flag = carve<unsigned char>(cur, Pn);
     d.changed = carve<int>(cur, Pn); d.orphans = carve<int>(cur, Pn); d.tiles_hit = carve<int>(cur, ntiles + 1);
@@ -2090,6 +2091,29 @@ int tdt_chain_set_exact_every(td_chain *ch, int k) {
     ch->dev.exact_every = k;
     ch->desc_dirty = true;
     return TD_OK;
+}
+
+// DevChain::own against a recount of best_s (both copied back): the slots where they differ
+int tdt_chain_own_check(td_chain *ch) {
+    if (!ch || ch->engine != TD_ENGINE_DEVICE) return -TD_ERR_ARG;
+    if (ch->prm.debug_prior == 1) return 0;  // (no forward state: neither array is kept)
+    td_ctx *c = ch->ctx;
+    const DevChain &d = ch->dev;
+    std::vector<int> bs((size_t)std::max(d.P, 0)), own((size_t)d.cap), cnt((size_t)d.cap, 0);
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && !bs.empty()) e = hipMemcpy(bs.data(), d.best_s, sizeof(int) * bs.size(), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && !own.empty()) e = hipMemcpy(own.data(), d.own, sizeof(int) * own.size(), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        hip_err(c, e, "tdt_chain_own_check");
+        return -TD_ERR_HIP;
+    }
+    int bad = 0;
+    for (int s : bs) {
+        if (s >= 0 && s < d.cap) cnt[(size_t)s] += 1;
+        else bad += 1;  // (a point with no owner: counted as a mismatch)
+    }
+    for (int s = 0; s < d.cap; ++s) bad += own[(size_t)s] != cnt[(size_t)s];
+    return bad;
 }
 
 int tdt_chain_lds(td_chain *ch, int64_t out[4]) {

@@ -54,6 +54,8 @@ struct ChainScalars {
                                // [66..67] wave-0 F timeline, [68..71] tiles hit, points seen/changed, rays changed,
                                // [72..75] chi^2 walk (rays in HBM): events, batch-load cycles, event-walk
                                // cycles, terms added one by one
+                               // [35] / [45] deaths / changes on the short road, [55] guesses adopted with the
+                               // barren flag up, [25] of those the ones cleared at adoption
     int ncells;            // cells in the model
     int nslots;            // slot high-water mark
     int nfree;             // free-slot stack depth
@@ -127,6 +129,12 @@ struct DevChain {
     int nsuper;
     // cells by slot
     double *cx, *cy, *cz, *czeta;  // [cap]
+    // own[slot] = the points whose nearest cell is the slot's: #{q : best_s[q] == slot} at every launch
+    // boundary (chain_full_state counts it, phase G's commits keep it); free and never-used slots hold 0.
+    // A change or death whose cell owns no point changes no ray: k_chain_run's short road.
+    // (beside the cell arrays: a guessed proposal fetches its cell's count with its coordinates, and the
+    // kernel reads the five pointers in one go)
+    int *own;  // [cap]
     const double *logN;            // [cap+2] det_log(k), the MH model-size factor
     int *order, *free_slots, *order_tmp;  // [cap]
     long long *stamp;                     // [cap]; -1 = a free slot

@@ -78,17 +78,20 @@ struct OverlayZeta {
 struct ProposalLoads {
     Proposal q;
     int s, new_slot;
+    int own;  // DevChain::own of the selected cell; -1: not asked (no guess), or a birth
     double x, y, z, ze;
 };
-template <class SlotAt>
+template <bool OWN = false, class SlotAt>
 __device__ __forceinline__ ProposalLoads proposal_begin(const tdchain::Params &P, const tdchain::Draws &dr,
                                                         int ncells, int nfree, int nslots, const int *free_slots,
                                                         const double *cx, const double *cy, const double *cz,
-                                                        const double *czeta, SlotAt slot_at) {
+                                                        const double *czeta, SlotAt slot_at,
+                                                        const int *own = nullptr) {
     ProposalLoads l;
     l.q = tdchain::propose(P, dr, ncells);
     l.s = -1;
     l.new_slot = -1;
+    l.own = -1;
     l.x = l.y = l.z = l.ze = 0.0;
     if (l.q.active && l.q.action != tdchain::kBirth) {  // (global loads: no LDS wait or barrier waits for them)
         l.s = slot_at((int)l.q.index);
@@ -96,6 +99,12 @@ __device__ __forceinline__ ProposalLoads proposal_begin(const tdchain::Params &P
         l.y = gload(cy + l.s);
         l.z = gload(cz + l.s);
         l.ze = gload(czeta + l.s);
+        // The cell's point count, in the same round trip.  Other waves of the workgroup keep it with atomics
+        // performed in L2 (phase G), so the read is an agent-scope atomic load: a plain load could be served
+        // from a line this CU's L1 has held since before them.
+        if constexpr (OWN)
+            l.own = __hip_atomic_load((const __attribute__((address_space(1))) int *)(own + l.s), __ATOMIC_RELAXED,
+                                      __HIP_MEMORY_SCOPE_AGENT);
     }
     if (l.q.active && l.q.action == tdchain::kBirth) l.new_slot = nfree > 0 ? gload(free_slots + nfree - 1) : nslots;
     return l;
@@ -105,6 +114,7 @@ __device__ __forceinline__ void proposal_end(PState &o, const tdchain::Params &P
     Proposal q = l.q;
     o.slot_k = -1;
     o.new_slot = l.new_slot;
+    o.barren = l.own == 0 ? 1 : 0;  // (trusted only once the guess is adopted: k_chain_run, the iteration's end)
     if (q.active && q.action != tdchain::kBirth) {
         o.slot_k = l.s;
         o.kx = l.x;
@@ -117,12 +127,12 @@ __device__ __forceinline__ void proposal_end(PState &o, const tdchain::Params &P
     // forward evaluation needed (birth validity is only known after its query)
     o.eval = q.active && (q.valid || q.action == tdchain::kBirth) && P.debug_prior != 1;
 }
-template <class SlotAt>
+template <bool OWN = false, class SlotAt>
 __device__ __forceinline__ void make_proposal(PState &o, const tdchain::Params &P, const tdchain::Draws &dr,
                                               int ncells, int nfree, int nslots, const int *free_slots,
                                               const double *cx, const double *cy, const double *cz,
-                                              const double *czeta, SlotAt slot_at) {
-    proposal_end(o, P, dr, proposal_begin(P, dr, ncells, nfree, nslots, free_slots, cx, cy, cz, czeta, slot_at));
+                                              const double *czeta, SlotAt slot_at, const int *own = nullptr) {
+    proposal_end(o, P, dr, proposal_begin<OWN>(P, dr, ncells, nfree, nslots, free_slots, cx, cy, cz, czeta, slot_at, own));
 }
 
 // A scripted step (td_evaluate's incremental path) as the proposal: always
@@ -141,6 +151,7 @@ __device__ __forceinline__ void script_proposal(PState &o, const ScriptStep &st,
     q.zeta = st.zeta;
     o.slot_k = -1;
     o.new_slot = -1;
+    o.barren = 0;
     if (q.action != tdchain::kBirth) {
         const int s = slot_at(st.index);
         o.slot_k = s;
@@ -680,6 +691,14 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
         bool nobar = false;  // phase B without its block barrier (block-uniform; below)
         int pre_q = 0, pre_ray = 0, pre_s = 0;
         double pre_bd = 0.0, pre_x = 0.0, pre_y = 0.0, pre_z = 0.0;
+        // The short road (block-uniform; free-running instances): a change or death whose cell owns no ray
+        // point (PState::barren, trusted) changes no point and no ray -- no tile pass, no b_done hand-off, no
+        // phases C-E; every counter stays 0 and k0 == n, so phase F decides on phi_n = phi_r as it does for any
+        // proposal that turned out empty, and phase G's loops are empty.  A death keeps its killed-site query
+        // and phase B's barrier (the decision reads the answer after it); a change goes straight to phase F,
+        // whose barrier is then the one between the loop top's reads and wave 0's end-of-iteration writes.
+        const bool sroad = !SCRIPT && cur.barren != 0 && p.active && p.valid && P.debug_prior != 1 &&
+                           (action == tdchain::kChange || action == tdchain::kDeath);
         if (p.active) {
             // ============ phase B: tile pass || birth/death Interpolation ============
             // (a scripted step brings its own values: no Interpolation query -- but for a server's death
@@ -692,8 +711,8 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
             // it walks the whole hit list: each wave counts itself done after its tile pass (a death's
             // query wave before its query, whose answer only the decision reads) and a wave waits for all
             // of them after its own points.  (A birth's marks need the query's answer: the barrier stays.)
-            nobar = kNoBarB && action != tdchain::kBirth && p.valid && P.debug_prior != 1;
-            if (eval) {
+            nobar = kNoBarB && action != tdchain::kBirth && p.valid && P.debug_prior != 1 && !sroad;
+            if (eval && !sroad) {
                 // tiles whose box can hold a point the proposal changes (the last
                 // wave answers the Interpolation query meanwhile)
                 const bool q0 = action != tdchain::kBirth;  // old site of the selected cell
@@ -882,7 +901,7 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
         // NEXT proposal.  So every iteration has a block barrier between the loop top and wave 0's
         // end-of-iteration writes (this one, or C's and F's).  Found by the wave-skew build
         // (tools/skew_probe.py, the 8-cell model at max_cells 12).
-        if (!nobar) {
+        if (!nobar && !(sroad && action == tdchain::kChange)) {  // (the short road's change: phase F's barrier)
             __syncthreads();
             SKEW(4);
             if (p.active && action == tdchain::kBirth) czeta = sh.q_zeta;
@@ -897,7 +916,7 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
         if (pp.active && pp.valid) {
             const bool fwd = P.debug_prior != 1;
             int no = 0;
-            if (fwd) {
+            if (fwd && !sroad) {
                 // ================= phase C: affected points =================
                 if (!nscript && tid == NTH - 64)  // the decision's phi-free part, off phase F's path
                     sh.ap = tdchain::alpha_parts(P, pp, czeta, zeta_killed,
@@ -913,9 +932,9 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
                 auto point = [&](int q, int ray, int s, double bd, double qx, double qy, double qz) {
                     if (action == tdchain::kBirth) {  // appended cell: strict capture
                         const double dd = dist2(pp.x, pp.y, pp.z, qx, qy, qz);
-                        if (dd < bd) mark(d, v, sh, q, ray, new_slot, dd, pp.zeta);
+                        if (dd < bd) mark(d, v, sh, q, ray, new_slot, dd, pp.zeta, s);
                     } else if (action == tdchain::kChange) {
-                        if (s == slot_k) mark(d, v, sh, q, ray, s, bd, pp.zeta);
+                        if (s == slot_k) mark(d, v, sh, q, ray, s, bd, pp.zeta, s);
                     } else if (s == slot_k) {  // death / move: its points are re-searched
                         const int o = atomicAdd(&sh.n_orphans, 1);
                         d.orphans[o] = q;
@@ -924,7 +943,7 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
                         const double dd = dist2(pp.x, pp.y, pp.z, qx, qy, qz);
                         // (an exact tie: Julia positions, through the stamps -- loaded only then)
                         if (dd < bd || (dd == bd && s >= 0 && d.stamp[slot_k] < d.stamp[s]))
-                            mark(d, v, sh, q, ray, slot_k, dd, zeta_k);
+                            mark(d, v, sh, q, ray, slot_k, dd, zeta_k, s);
                     }
                 };
                 if constexpr (SMALL) {
@@ -1123,7 +1142,7 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
                                     if (bs >= 0 && bd < kSentinel && !tie && bd < lb) {
                                         const int q = o < kOrphanLds ? sh.orph[o].q : d.orphans[o];
                                         const int ray = o < kOrphanLds ? sh.orph[o].ray : d.pt_ray[q];
-                                        mark(d, v, sh, q, ray, bs, bd, d.czeta[bs]);
+                                        mark(d, v, sh, q, ray, bs, bd, d.czeta[bs], slot_k);
                                     } else {
                                         fb[atomicAdd(&sh.ob_nfb, 1)] = o;
                                     }
@@ -1155,7 +1174,7 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
                     }
                     const Nearest r =
                         wave_nearest(d, v, sh, lane, qx, qy, qz, skip_s, moved_s, pp.x, pp.y, pp.z, zeta_killed);
-                    if (lane == 0) mark(d, v, sh, q, ray, r.s, r.d, r.z);
+                    if (lane == 0) mark(d, v, sh, q, ray, r.s, r.d, r.z, slot_k);  // (an orphan: its owner was the selected cell)
                 }
                 if (nlist > 0) __syncthreads();
                 SKEW(10);
@@ -1468,8 +1487,10 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
                 if (prof_on && bdec == 1) atomicAdd((unsigned long long *)&sh.prof[14], 1ull);  // rejected on bounds
             } else if (spec_in_F && tid == 64) {  // the next proposal as if this one were rejected
                 if (can_spec) {
-                    make_proposal(sh.ps[sh.cur ^ 1], P, draws[(it + 1) & 63], ncells, sh.nfree, sh.nslots, d.free_slots, d.cx,
-                                  d.cy, d.cz, d.czeta, [&](int pos) { return v.ord[pos]; });
+                    // (with the cell's point count: every commit atomic of earlier iterations is performed --
+                    // phase G's waves wait for theirs before the iteration-end barrier)
+                    make_proposal<true>(sh.ps[sh.cur ^ 1], P, draws[(it + 1) & 63], ncells, sh.nfree, sh.nslots,
+                                        d.free_slots, d.cx, d.cy, d.cz, d.czeta, [&](int pos) { return v.ord[pos]; }, d.own);
                     sh.spec_ok = 1;
                 }
             } else if (wv == kWv - 1 || (kWv >= 6 && wv == kWv - 2)) {
@@ -1480,6 +1501,7 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
                                   kz, pp.x, pp.y, pp.z);
                 if (wv == (kWv >= 6 ? kWv - 2 : kWv - 1)) {
                     if (prof_on && lane == 0) {  // diagnostic: work sizes
+                        if (sroad) sh.prof[action == tdchain::kDeath ? 35 : 45] += 1;  // the short road, by action
                         sh.prof[68] += sh.n_tiles;
                         sh.prof[69] += sh.pts_seen;
                         sh.prof[70] += sh.n_changed;
@@ -1490,12 +1512,20 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
                         // bytes this proposal's algorithm must read: tile boxes + maxima (32 B),
                         // candidate points (coords + cached slot/distance, 36 B), grid queries
                         // (27 buckets x 8 entries x 32 B), rays (w, zeta, flag: 17 B per point),
-                        // chi^2 tail (ptS, tS, sig, flag: 28 B per ray)
+                        // chi^2 tail (ptS, tS, sig, flag: 28 B per ray).  A change or death whose cell owns no
+                        // point needs no tile box and no point: counted so on either road -- the full path,
+                        // which finds it out (nothing marked, no orphan), reads them for nothing -- so the
+                        // count does not depend on which proposals a launch's first or an untrusted guess is
+                        // (tests/test_gpu_tempering_history.py holds the stats of split calls to one call's)
+                        // (scripted steps always take the full path: counted as before)
+                        const bool owns_none = !SCRIPT && ((action == tdchain::kChange && sh.n_changed == 0) ||
+                                                          (action == tdchain::kDeath && no == 0));
                         atomicAdd((unsigned long long *)&sh.bytes,
-                                  (unsigned long long)((super_on ? (long long)NS * 32 +
-                                                                      (long long)sh.n_super[it & 1] * kTilePts * 32
-                                                                 : (long long)NT * 32) +
-                                                       (long long)sh.pts_seen * 36 +
+                                  (unsigned long long)((owns_none  ? 0ll
+                                                        : super_on ? (long long)NS * 32 +
+                                                                         (long long)sh.n_super[it & 1] * kTilePts * 32 +
+                                                                         (long long)sh.pts_seen * 36
+                                                                   : (long long)NT * 32 + (long long)sh.pts_seen * 36) +
                                                        (long long)(no + (action <= 2 ? 1 : 0)) * 27 * 8 * 32 +
                                                        (RLDS ? 0ll : (long long)sh.ray_pts * 17) + (long long)(n - sh.k0) * 28));
                     }
@@ -1573,22 +1603,41 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
             const int w = tid - 64;
             if (sh.gs.accept) {
                 const int nt = sh.gs.nt, k0 = sh.gs.k0;
-                if (wv != 0)
+                if (wv != 0) {
+                    // DevChain::own follows every point whose owner changes: two no-return atomics in L2 (an
+                    // accepted change moves no owner -- block-uniform).  The old owner came with the record
+                    // (LDS), or is loaded beside the overlay (HBM: the same round trip, before the store).
+                    const bool owners = action != tdchain::kChange;
                     for (int c = w; c < nc; c += kW) {
+                        int so, sn;
                         if (c < kChgLds) {  // (LDS: stores only)
                             const ChgRec r = sh.chg[c];
                             d.best_s[r.q] = r.s;
                             d.best_d[r.q] = r.d;
                             d.zeta0[r.q] = r.z;
                             d.cand_flag[r.q] = 0;
+                            so = r.o;
+                            sn = r.s;
                         } else {
                             const int q = d.changed[c];
-                            d.best_s[q] = d.cand_s[q];
+                            so = d.best_s[q];
+                            sn = d.cand_s[q];
+                            d.best_s[q] = sn;
                             d.best_d[q] = d.cand_d[q];
                             d.zeta0[q] = d.cand_z[q];
                             d.cand_flag[q] = 0;
                         }
+                        if (owners && so != sn) {
+                            if (so >= 0) atomicAdd(&d.own[so], -1);
+                            if (sn >= 0) atomicAdd(&d.own[sn], 1);
+                        }
                     }
+                    // The next iteration's guess reads own in phase F (tid 64), and its flag is trusted when
+                    // that iteration changes no owner: these atomics must be performed by then.  Counted in
+                    // vmcnt like stores, they are waited for here, before this wave reaches the
+                    // iteration-end barrier -- the s_barrier alone orders nothing in the vector memory pipe.
+                    if (owners && w < nc) __builtin_amdgcn_s_waitcnt(0);
+                }
                 if (fwd && action != tdchain::kChange) {
                     for (int i = tid; i < nt; i += NTH) v.tmaxd[v.tile_rec(i).x] = v.ctm_at(i);
                     pend_sup = super_on;  // their super-tiles' maxima: at the top of the next iteration
@@ -1790,6 +1839,16 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
                     if (keep) {
                         cur_r ^= 1;  // adopt the guess: no copy
                         sh.cur = cur_r;
+                        // Its barren flag holds what own[] said in phase F, before this iteration's commit: it
+                        // stays only if the commit moved no owner -- a rejection, an accepted change, or an
+                        // accepted proposal that changed no point (a kept guess follows nothing else but a
+                        // move).  Else the proposal takes the full path, which is right whatever the flag.
+                        // (The flag is not read here: cleared whether up or not, off the common path.)
+                        if (prof_on && g.barren) sh.prof[55] += 1;  // diagnostic: guesses adopted with the flag up
+                        if (acc && action != tdchain::kChange && sh.gs.nc != 0) {
+                            if (prof_on && g.barren) sh.prof[25] += 1;  // diagnostic: ... and cleared here
+                            sh.ps[cur_r].barren = 0;
+                        }
                     } else {
                         // a just-killed position (LDS layout; in the HBM order phase G has shifted it already):
                         // scripted steps read the staged pre-shift order; a free-running chain the order once

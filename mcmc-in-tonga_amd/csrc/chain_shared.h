@@ -42,9 +42,11 @@ constexpr bool kSmallWalk = false;
 // A changed point's candidate (what mark() stores in the overlay), kept in LDS for the first kChgLds of
 // a proposal: phase G commits them from here with stores only -- no dependent round trips to the
 // changed list and the overlay in HBM
+// (o: the point's owner before the proposal -- what phase G needs to keep DevChain::own without a load)
 struct ChgRec {
     int q, s;
     double d, z;
+    int o;
 };
 constexpr int kChgLds = 64;
 
@@ -75,6 +77,11 @@ struct PState {
     Proposal p;
     double kx, ky, kz, zeta_killed;  // site and value of the selected cell (not birth)
     int slot_k, new_slot, eval;
+    // the selected cell owned no ray point (DevChain::own) when the proposal was made AND nothing can have
+    // changed ownership since: set only on a guess of phase F, cleared at its adoption unless the iteration
+    // it was made in left every owner alone (k_chain_run, the iteration's end).  A change or death with it
+    // set changes no ray: it takes the short road (no tile pass, no phases C-E)
+    int barren;
 };
 
 // The bucket grid's geometry and arrays, copied into LDS when a launch starts: a query reads them in

@@ -1,5 +1,5 @@
 // chain_state.hip -- the device chain's full state from scratch (chain_full_state: nearest search, ray
-// sums, then the chi^2 prefix sums and tile maxima computed here), and the LDS sizes a chain's launches
+// sums, then the cells' point counts, the chi^2 prefix sums and tile maxima computed here), and the LDS sizes a chain's launches
 // take.  The chain itself, and its one-point query, are in chain_kernels.hip.
 #pragma clang fp contract(off)
 
@@ -48,6 +48,14 @@ __global__ void k_tile_max(const int *__restrict__ tile_start, int ntiles, const
     tile_maxd[t] = mx;
 }
 
+// own[slot] = #{q : best_s[q] == slot} (chain_dev.h), over zeroed counts
+__global__ __launch_bounds__(256) void k_own_count(const int *__restrict__ best_s, int P, int cap, int *__restrict__ own) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= P) return;
+    const int s = best_s[q];
+    if (s >= 0 && s < cap) atomicAdd(&own[s], 1);
+}
+
 }  // namespace
 
 hipError_t launch_chi2_prefix(const double *ptS, const double *tS, const double *sig, int n, double *prefix,
@@ -72,6 +80,13 @@ hipError_t chain_full_state(DevChain &d, int ncells, NNWork &work, int num_cus, 
     hipError_t e = launch_nearest(d.px, d.py, d.pz, d.P, 1, 1, d.cx, d.cap, ncells, work, num_cus, d.best_s,
                                   d.best_d, d.zeta0, s);
     if (e != hipSuccess) return e;
+    e = hipMemsetAsync(d.own, 0, sizeof(int) * (size_t)d.cap, s);
+    if (e != hipSuccess) return e;
+    if (d.P > 0) {
+        hipLaunchKernelGGL(k_own_count, dim3((d.P + 255) / 256), dim3(256), 0, s, d.best_s, d.P, d.cap, d.own);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
     e = launch_ray_sums(g, d.zeta0, d.ptS, s);
     if (e != hipSuccess) return e;
     e = launch_chi2_prefix(d.ptS, d.tS, d.sig, d.n, d.prefix, d.st, s);

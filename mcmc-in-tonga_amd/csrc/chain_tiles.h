@@ -11,14 +11,14 @@ namespace tdstar {
 namespace {
 
 __device__ __forceinline__ void mark(const DevChain &d, const Views &v, Shared &sh, int p, int r, int s, double dd,
-                                     double z) {
+                                     double z, int o) {
     d.cand_s[p] = s;
     d.cand_d[p] = dd;
     d.cand_z[p] = z;
     d.cand_flag[p] = 1;
     const int c = atomicAdd(&sh.n_changed, 1);
     d.changed[c] = p;
-    if (c < kChgLds) sh.chg[c] = ChgRec{p, s, dd, z};
+    if (c < kChgLds) sh.chg[c] = ChgRec{p, s, dd, z, o};
     if (atomicExch(&v.rflag[r], 1) == 0) {
         v.ray_put(atomicAdd(&sh.n_rays, 1), r);
         atomicMin(&sh.k0, r);
