@@ -15,8 +15,6 @@
 
 #include "chain_dev.h"
 #include "ctx.h"
-#include "predict.h"
-#include "volume.h"
 
 namespace {
 thread_local std::string g_err;  // td_create failures (no ctx yet)
@@ -325,17 +323,15 @@ void free_ctx(td_ctx *c) {
     if (!c) return;
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     shadow_free(c);
-    volume_free(c);
-    predict_free(c);
     c->timer.release();
     void *dev[] = {c->g.px, c->g.py, c->g.pz, c->g.w, c->g.ray_off, c->g.tS, c->g.sig, c->g.terms, c->cells,
                    c->nn.part_d, c->nn.part_i, c->best_i, c->best_d, c->zeta0, c->phi,
-                   c->q, c->q_i, c->q_z, c->chain_desc, c->draws, c->nn.g_count, c->nn.g_ent, c->raster, c->raster_i, c->raster_off,
-                   c->mf_dev, c->marg, c->conv};
+                   c->q, c->q_i, c->q_z, c->chain_desc, c->draws, c->nn.g_count, c->nn.g_ent, c->mf_dev,
+                   c->raster.p, c->raster_i.p, c->raster_off.p, c->marg.p, c->conv.p, c->vol.p, c->vol_grid.p, c->pred.p};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     void *host[] = {c->h_cells, c->h_out, c->h_best_i, c->h_q, c->h_q_i, c->h_q_z, c->h_chain_desc, c->mf_host,
-                    c->h_raster, c->h_conv};
+                    c->h_raster.p, c->h_conv.p};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);

@@ -18,13 +18,6 @@ struct ConvPlan {
     double tau_floor = 0.0;          // 1 / log10(m n)
 };
 
-// a rasterising entry point's request, beside td_marginals in rasterize_core
-struct ConvRequest {
-    int64_t nchains;
-    const int64_t *chain_len;
-    const td_convergence *want;
-};
-
 // The lengths must already have passed conv_check_chains.
 void conv_plan(int64_t nchains, const int64_t *chain_len, int64_t max_lag, ConvPlan *plan);
 
@@ -37,8 +30,5 @@ int conv_check_chains(td_ctx *ctx, int64_t nchains, const int64_t *chain_len, in
 // synchronises at the end.
 int convergence_run(td_ctx *ctx, const double *values, int64_t M, int64_t ncol, int64_t nchains,
                     const int64_t *chain_len, const td_convergence *want);
-
-// raster.hip: room for nd doubles in ctx->raster and nh doubles in the pinned ctx->h_raster
-int raster_reserve(td_ctx *ctx, size_t nd, size_t nh);
 
 }  // namespace tdstar

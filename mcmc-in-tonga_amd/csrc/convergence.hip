@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "convergence.h"
+#include "volume.h"
 
 namespace tdstar {
 
@@ -200,24 +201,6 @@ __global__ __launch_bounds__(64) void k_geyer(const double *__restrict__ acov, i
     }
 }
 
-int ensure_conv(td_ctx *ctx, size_t bytes, size_t host_bytes) {
-    if (bytes > ctx->conv_cap) {
-        if (ctx->conv) (void)hipFree(ctx->conv);
-        ctx->conv = nullptr;
-        ctx->conv_cap = 0;
-        TD_HIP(ctx, hipMalloc(&ctx->conv, bytes));
-        ctx->conv_cap = bytes;
-    }
-    if (host_bytes > ctx->h_conv_cap) {
-        if (ctx->h_conv) (void)hipHostFree(ctx->h_conv);
-        ctx->h_conv = nullptr;
-        ctx->h_conv_cap = 0;
-        TD_HIP(ctx, hipHostMalloc(&ctx->h_conv, host_bytes, hipHostMallocDefault));
-        ctx->h_conv_cap = host_bytes;
-    }
-    return TD_OK;
-}
-
 template <int LB>
 void launch_autocov(td_ctx *ctx, dim3 grid, const double *V, int ncol, int n, const long long *seq, const double *mean,
                     int t_lo, int t_hi, int base, int R, double *acov, const int *tile_active) {
@@ -297,15 +280,16 @@ int convergence_run(td_ctx *ctx, const double *values, int64_t M, int64_t ncol64
     const size_t mc = (size_t)m * ncol, nd = 2 * mc + 6 * (size_t)ncol + mc * (size_t)R;
     const size_t ni = 3 * (size_t)ncol + (size_t)ntiles + 1;
     const size_t host_b = 8 + sizeof(int64_t) * (size_t)m;
-    if (int rc = ensure_conv(ctx, sizeof(double) * nd + sizeof(int64_t) * (size_t)m + sizeof(int) * ni, host_b)) return rc;
-    double *dmean = static_cast<double *>(ctx->conv), *dvar = dmean + mc, *dW = dvar + mc, *dvp = dW + ncol,
+    if (int rc = grow(ctx, ctx->conv, sizeof(double) * nd + sizeof(int64_t) * (size_t)m + sizeof(int) * ni)) return rc;
+    if (int rc = grow(ctx, ctx->h_conv, host_b)) return rc;
+    double *dmean = ctx->conv.as<double>(), *dvar = dmean + mc, *dW = dvar + mc, *dvp = dW + ncol,
            *dS = dvp + ncol, *dPp = dS + ncol, *drhat = dPp + ncol, *dess = drhat + ncol, *dacov = dess + ncol;
     long long *dseq = reinterpret_cast<long long *>(dacov + mc * (size_t)R);
     int *dlast = reinterpret_cast<int *>(dseq + m), *dstopped = dlast + ncol, *dlags = dstopped + ncol,
         *dtile = dlags + ncol, *dcount = dtile + ntiles;
     TD_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the pinned block may still feed a previous copy
-    int *hcount = static_cast<int *>(ctx->h_conv);
-    int64_t *hseq = reinterpret_cast<int64_t *>(static_cast<char *>(ctx->h_conv) + 8);
+    int *hcount = ctx->h_conv.as<int>();
+    int64_t *hseq = reinterpret_cast<int64_t *>(ctx->h_conv.as<char>() + 8);
     std::memcpy(hseq, p.seq_start.data(), sizeof(int64_t) * (size_t)m);
     TD_HIP(ctx, hipMemcpyAsync(dseq, hseq, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
     Timer *tm = ctx->timer.on ? &ctx->timer : nullptr;
@@ -367,9 +351,9 @@ extern "C" int td_convergence_values(td_ctx *ctx, const double *values, int64_t 
     const size_t nv = (size_t)M * (size_t)ncol;
     if (int rc = raster_reserve(ctx, nv, nv)) return rc;
     TD_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the staging block may still feed a previous copy
-    std::memcpy(ctx->h_raster, values, sizeof(double) * nv);
-    TD_HIP(ctx, hipMemcpyAsync(ctx->raster, ctx->h_raster, sizeof(double) * nv, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = convergence_run(ctx, ctx->raster, M, ncol, nchains, chain_len, want)) return rc;
+    std::memcpy(ctx->h_raster.p, values, sizeof(double) * nv);
+    TD_HIP(ctx, hipMemcpyAsync(ctx->raster.p, ctx->h_raster.p, sizeof(double) * nv, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = convergence_run(ctx, ctx->raster.as<double>(), M, ncol, nchains, chain_len, want)) return rc;
     TD_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return TD_OK;
 }

@@ -37,6 +37,7 @@
 #include "convergence.h"
 #include "covariance.h"
 #include "ctx.h"
+#include "ensemble.h"
 #include "history.h"
 #include "volume.h"
 
@@ -215,13 +216,11 @@ hipError_t timed_stats(td_ctx *ctx, const double *values, int nmodels, int n, do
     return e;
 }
 
-// Both entry points (volume_build's arguments); every argument has been checked.
-int cov_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *cell_off, const double *xCell,
-             const double *yCell, const double *zCell, const double *zeta, const std::vector<td_history *> *segs,
-             const td_covariance *cv) {
+// Both entry points; E and cv have been checked (ensemble.h, cov_check).
+int cov_core(td_ctx *ctx, const char *who, const Ensemble &E, const td_covariance *cv) {
     constexpr int G = kCovGroup;
     const std::string w(who);
-    const int64_t M = nmodels, nq = cv->nq, nt = cv->nt, T = cv->nt + cv->nseries;
+    const int64_t M = E.nmodels, nq = cv->nq, nt = cv->nt, T = cv->nt + cv->nseries;
     if (T > INT32_MAX - 64) return set_err(ctx, TD_ERR_ARG, w + ": too many targets");
     const size_t lds = sizeof(double) * (size_t)(1 + cov_levels(M)) * G * kCovThreads;  // the tile | the levels
     if (lds > 64 * 1024) return set_err(ctx, TD_ERR_ARG, w + ": more than 2^25 models");  // (15 levels: 64 KiB of LDS)
@@ -229,7 +228,7 @@ int cov_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *cell_
     TD_HIP(ctx, hipSetDevice(ctx->device));
     servers_quiesce(nullptr);
     VolSearch S;
-    if (int rc = volume_build(ctx, who, M, cell_off, xCell, yCell, zCell, zeta, segs, &S)) return rc;
+    if (int rc = volume_build(ctx, who, E, &S)) return rc;
     hipStream_t s = ctx->stream;
     Timer *tm = ctx->timer.on ? &ctx->timer : nullptr;
     const VolPlan plan = volume_plan(M, nq, kVolDefaultBudget, ctx->vol_slab_nodes);
@@ -241,17 +240,14 @@ int cov_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *cell_
     const size_t n_slab = (size_t)cap * (5 + (size_t)M), n_A = (size_t)M * (size_t)T,
                  n_Ac = nq > 0 ? (size_t)ngroups * (size_t)M * G : 0, n_out = (size_t)T * (size_t)capq;
     if (int rc = raster_reserve(ctx, n_slab + n_A + 2 * (size_t)T + n_Ac + 2 * n_out, 3 * (size_t)cap + 2 * n_out)) return rc;
-    double *dAc = ctx->raster, *dq = dAc + n_Ac, *dv = dq + 3 * cap, *dm = dv + M * cap, *dsd = dm + cap;
+    double *dAc = ctx->raster.as<double>(), *dq = dAc + n_Ac, *dv = dq + 3 * cap, *dm = dv + M * cap, *dsd = dm + cap;
     double *dA = dsd + cap, *dmt = dA + n_A, *dst = dmt + T, *dcov = dst + T, *dcorr = dcov + n_out;
-    double *h = ctx->h_raster, *hcov = h + 3 * cap, *hcorr = hcov + n_out;
+    double *hcov = ctx->h_raster.as<double>() + 3 * cap, *hcorr = hcov + n_out;
     int64_t brute_pairs = 0;
     // the targets: the points swept as query blocks into A[:, 0:nt], the caller's series beside them
     for (int64_t t0 = 0; t0 < nt; t0 += plan.nodes) {
         const int64_t nts = std::min(plan.nodes, nt - t0);
-        std::memcpy(h, cv->tx + t0, sizeof(double) * (size_t)nts);
-        std::memcpy(h + nts, cv->ty + t0, sizeof(double) * (size_t)nts);
-        std::memcpy(h + 2 * nts, cv->tz + t0, sizeof(double) * (size_t)nts);
-        TD_HIP(ctx, hipMemcpyAsync(dq, h, sizeof(double) * 3 * (size_t)nts, hipMemcpyHostToDevice, s));
+        if (int rc = stage_queries(ctx, cv->tx, cv->ty, cv->tz, t0, nts, dq)) return rc;
         if (int rc = volume_sweep(ctx, S, 0, M, dq, nts, dv)) return rc;
         if (!S.grid) brute_pairs += M * nts;
         TD_HIP(ctx, hipMemcpy2DAsync(dA + t0, sizeof(double) * (size_t)T, dv, sizeof(double) * (size_t)nts,
@@ -276,10 +272,7 @@ int cov_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *cell_
     }
     for (int64_t q0 = 0; q0 < nq; q0 += plan.nodes) {
         const int64_t ns = std::min(plan.nodes, nq - q0);
-        std::memcpy(h, cv->qx + q0, sizeof(double) * (size_t)ns);
-        std::memcpy(h + ns, cv->qy + q0, sizeof(double) * (size_t)ns);
-        std::memcpy(h + 2 * ns, cv->qz + q0, sizeof(double) * (size_t)ns);
-        TD_HIP(ctx, hipMemcpyAsync(dq, h, sizeof(double) * 3 * (size_t)ns, hipMemcpyHostToDevice, s));
+        if (int rc = stage_queries(ctx, cv->qx, cv->qy, cv->qz, q0, ns, dq)) return rc;
         if (int rc = volume_sweep(ctx, S, 0, M, dq, ns, dv)) return rc;
         if (!S.grid) brute_pairs += M * ns;
         TD_HIP(ctx, timed_stats(ctx, dv, (int)M, (int)ns, dm, dsd));
@@ -307,11 +300,7 @@ int cov_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *cell_
         }
     }
     TD_HIP(ctx, hipStreamSynchronize(s));
-    unsigned long long cnt[4] = {0, 0, 0, 0};  // (tdt_volume_counters: the last call's, this one's sweeps too)
-    TD_HIP(ctx, hipMemcpy(cnt, S.counters, sizeof cnt, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 3; ++k) ctx->vol_counters[k] = S.grid && !ctx->vol_counting ? -1 : (int64_t)cnt[k];
-    ctx->vol_counters[3] = brute_pairs;
-    return TD_OK;
+    return volume_counters_finish(ctx, S, brute_pairs);  // (tdt_volume_counters: the last call's, this one's sweeps too)
 }
 
 }  // namespace
@@ -331,42 +320,20 @@ extern "C" int td_rasterize_covariance(td_ctx *ctx, int64_t nmodels, const int64
                                        const td_covariance *cov) {
     const char *who = "td_rasterize_covariance";
     if (int rc = cov_check(ctx, cov, who)) return rc;
-    const std::string w(who);
-    if (nmodels >= 1 && cell_off) {
-        const int64_t total = cell_off[nmodels];
-        if (cell_off[0] != 0 || total < 0 || (total > 0 && (!xCell || !yCell || !zCell || !zeta)))
-            return set_err(ctx, TD_ERR_ARG, w + ": bad cell offsets or arrays");
-        for (int64_t k = 0; k < nmodels; ++k)
-            if (cell_off[k + 1] < cell_off[k]) return set_err(ctx, TD_ERR_ARG, w + ": offsets not monotone");
-    }
-    if (nmodels < 1 || !cell_off) return set_err(ctx, TD_ERR_ARG, w + ": need nmodels >= 1 and cell_off");
-    if (!ctx) return set_err(nullptr, TD_ERR_ARG, w + ": ctx is NULL");
-    return cov_core(ctx, who, nmodels, cell_off, xCell, yCell, zCell, zeta, nullptr, cov);
+    if (int rc = ensemble_check_arrays(ctx, who, nmodels, cell_off, xCell, yCell, zCell, zeta)) return rc;
+    if (!ctx) return set_err(nullptr, TD_ERR_ARG, std::string(who) + ": ctx is NULL");
+    return cov_core(ctx, who, Ensemble(nmodels, cell_off, xCell, yCell, zCell, zeta), cov);
 }
 
 extern "C" int td_history_covariance(td_ctx *ctx, td_history *const *hs, int64_t nh, const td_covariance *cov) {
     const char *who = "td_history_covariance";
     if (int rc = cov_check(ctx, cov, who)) return rc;
-    const std::string w(who);
-    std::vector<td_history *> segs;
-    std::vector<int64_t> off(1, 0);  // the concatenation's prefix, from the histories' host mirrors
-    for (int64_t i = 0; hs && i < nh; ++i) {
-        td_history *h = hs[i];
-        if (!h) return set_err(ctx, TD_ERR_ARG, w + ": a history is NULL");
-        const int64_t base = off.back();
-        for (int64_t k = 1; k <= h->samples; ++k) off.push_back(base + h->off[(size_t)k]);
-        if (h->samples > 0) segs.push_back(h);  // (one without samples is skipped)
-    }
-    const int64_t nmodels = (int64_t)off.size() - 1;
-    if (nmodels < 1) return set_err(ctx, TD_ERR_ARG, w + ": the histories hold no sample");
-    // any context's history on one device, the context's: only its cells and offsets are read
-    const int device = ctx ? ctx->device : segs[0]->ctx->device;
-    for (td_history *h : segs)
-        if (h->ctx->device != device) return set_err(ctx, TD_ERR_ARG, w + ": every history must live on the context's device");
-    if (!ctx) return set_err(nullptr, TD_ERR_ARG, w + ": ctx is NULL");
-    for (td_history *h : segs)
-        if (h->ctx != ctx) TD_HIP(ctx, hipStreamSynchronize(h->ctx->stream));  // (what recorded it has ended)
-    return cov_core(ctx, who, nmodels, off.data(), nullptr, nullptr, nullptr, nullptr, &segs, cov);
+    Ensemble E;
+    if (int rc = ensemble_from_histories(ctx, who, hs, nh, HistoryRule::SameDevice, &E)) return rc;
+    if (int rc = ensemble_check_device(ctx, who, E)) return rc;  // (of the first history's device without a context)
+    if (!ctx) return set_err(nullptr, TD_ERR_ARG, std::string(who) + ": ctx is NULL");
+    if (int rc = ensemble_sync_foreign(ctx, E)) return rc;
+    return cov_core(ctx, who, E, cov);
 }
 
 extern "C" int tdt_covariance_group(void) { return kCovGroup; }

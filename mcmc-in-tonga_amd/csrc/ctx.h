@@ -11,7 +11,18 @@
 
 namespace tdstar {
 struct td_shadow;
-}
+// A workspace that only grows (grow, below): device memory and pinned host memory, capacities in bytes.
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    template <class T> T *as() const { return static_cast<T *>(p); }
+};
+struct PinnedBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    template <class T> T *as() const { return static_cast<T *>(p); }
+};
+}  // namespace tdstar
 
 struct td_ctx {
     int device = 0;
@@ -52,22 +63,15 @@ struct td_ctx {
     double *h_q_z = nullptr;
 
     tdstar::Timer timer;                // per-kernel HIP-event timing (td_timing_*)
-    double *raster = nullptr;           // td_rasterize workspace (doubles)
-    size_t raster_cap = 0;
-    int *raster_i = nullptr;
-    int64_t raster_i_cap = 0;
-    int64_t *raster_off = nullptr;      // td_rasterize: the models' cell offsets (batched search)
-    int64_t raster_off_cap = 0;
-    double *h_raster = nullptr;         // td_rasterize: pinned staging of queries and cells
-    size_t h_raster_cap = 0;
-    void *marg = nullptr;               // marginals.hip workspace: rank parameters | quantiles | histogram counts
-    size_t marg_cap = 0;                // bytes
+    tdstar::DevBuf raster;              // td_rasterize workspace (doubles); the slabs of the volume, predictive and covariance calls
+    tdstar::DevBuf raster_i;            // td_rasterize: nearest-cell indices of the per-model search (not returned)
+    tdstar::DevBuf raster_off;          // td_rasterize: the models' cell offsets (batched search)
+    tdstar::PinnedBuf h_raster;         // td_rasterize: pinned staging of queries and cells
+    tdstar::DevBuf marg;                // marginals.hip workspace: rank parameters | quantiles | histogram counts
     std::vector<unsigned char> marg_par_h;  // host copy of the rank parameters (the source of an async copy)
     int marg_method = 0;                // quantile regime: 0 auto, 1 resident, 2 streaming (tdt_set_marginals_method)
-    void *conv = nullptr;               // convergence.hip workspace: moments | round state | acov | sequence rows | flags
-    size_t conv_cap = 0;                // bytes
-    void *h_conv = nullptr;             // pinned: the count of active columns | the sequences' first rows
-    size_t h_conv_cap = 0;              // bytes
+    tdstar::DevBuf conv;                // convergence.hip workspace: moments | round state | acov | sequence rows | flags
+    tdstar::PinnedBuf h_conv;           // pinned: the count of active columns | the sequences' first rows
     int64_t conv_round = 0;             // lags per round, 0 auto (tdt_set_convergence_round)
     int conv_lb = 0;                    // lags per wave, 0 auto, 8 or 16 (tdt_set_convergence_lag_block)
     double cell_lo[3] = {0, 0, 0}, cell_hi[3] = {0, 0, 0};  // box of the uploaded cells (NaN skipped)
@@ -95,17 +99,14 @@ struct td_ctx {
     double mf_likelihood = 0.0;
     std::string err;
     // td_rasterize_volume / td_history_volume (volume.hip)
-    void *vol = nullptr;                // all models' cells SoA | offsets | boxes | grids | bucket prefix | path counters
-    size_t vol_cap = 0;                 // bytes
-    void *vol_grid = nullptr;           // bucket starts | cursors | the compact entries
-    size_t vol_grid_cap = 0;            // bytes
+    tdstar::DevBuf vol;                 // all models' cells SoA | offsets | boxes | grids | bucket prefix | path counters
+    tdstar::DevBuf vol_grid;            // bucket starts | cursors | the compact entries
     int64_t vol_slab_nodes = 0;         // nodes per slab, 0 auto (tdt_set_volume_slab_nodes)
     int vol_method = 0;                 // the sweep: 0 auto, 1 bucket grids, 2 brute force (tdt_set_volume_method)
     int vol_counting = 0;               // 1: the k_vol_search instance that counts its paths (tdt_set_volume_counting)
     int64_t vol_counters[4] = {0, 0, 0, 0};  // the last call's (model, node) pairs per path (tdt_volume_counters)
     // td_rasterize_predict / td_history_predict (predict.hip)
-    void *pred = nullptr;               // ptS [nmodels][n] | phi [nmodels] | mean, std [n]
-    size_t pred_cap = 0;                // bytes
+    tdstar::DevBuf pred;                // ptS [nmodels][n] | phi [nmodels] | mean, std [n]
     int64_t pred_slab_points = 0;       // points per slab, 0 auto (tdt_set_predict_plan)
     int64_t pred_model_chunk = 0;       // models per sweep, 0 auto (tdt_set_predict_plan)
     int pred_placement = 0;             // k_pred_ray_sums: 0 a model's blocks follow each other, 1 on XCD m % 8
@@ -123,6 +124,24 @@ int hip_err(td_ctx *ctx, hipError_t e, const char *what);
         hipError_t e_ = (call);                           \
         if (e_ != hipSuccess) return hip_err(ctx, e_, #call); \
     } while (0)
+// Room for `bytes` in a grow-only workspace: nothing is allocated when they fit, a buffer never
+// shrinks, and a failed allocation leaves the pointer null and the capacity 0.  td_destroy frees them.
+inline int grow(td_ctx *ctx, DevBuf &b, size_t bytes) {
+    if (bytes <= b.cap) return TD_OK;
+    if (b.p) (void)hipFree(b.p);
+    b = DevBuf{};
+    TD_HIP(ctx, hipMalloc(&b.p, bytes));
+    b.cap = bytes;
+    return TD_OK;
+}
+inline int grow(td_ctx *ctx, PinnedBuf &b, size_t bytes) {
+    if (bytes <= b.cap) return TD_OK;
+    if (b.p) (void)hipHostFree(b.p);
+    b = PinnedBuf{};
+    TD_HIP(ctx, hipHostMalloc(&b.p, bytes, hipHostMallocDefault));
+    b.cap = bytes;
+    return TD_OK;
+}
 // Make room for `ncells` cells (device + pinned staging).
 int ensure_cells(td_ctx *ctx, int64_t ncells);
 // Pack cells into the pinned staging buffer and upload them (async on ctx->stream).

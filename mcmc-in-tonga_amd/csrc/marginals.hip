@@ -184,16 +184,6 @@ __global__ __launch_bounds__(256) void k_zeta_hist(const double *__restrict__ ze
         if (cnt[s]) atomicAdd(&hist[s], (unsigned long long)cnt[s]);
 }
 
-int ensure_marg(td_ctx *ctx, size_t bytes) {
-    if (bytes <= ctx->marg_cap) return TD_OK;
-    if (ctx->marg) (void)hipFree(ctx->marg);
-    ctx->marg = nullptr;
-    ctx->marg_cap = 0;
-    TD_HIP(ctx, hipMalloc(&ctx->marg, bytes));
-    ctx->marg_cap = bytes;
-    return TD_OK;
-}
-
 int allow_lds(td_ctx *ctx, const void *kern, size_t lds) {
     if (lds > 48 * 1024)
         TD_HIP(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -249,10 +239,10 @@ int marginals_run(td_ctx *ctx, const double *values, int64_t M, int64_t nq, cons
     if (int rc = marg_check_models(ctx, want, M)) return rc;  // (the entry points have made it already)
     const size_t par_b = sizeof(QuantPar), quant_b = sizeof(double) * (size_t)nprob * nq,
                  hist_b = nbins > 0 ? sizeof(int64_t) * (size_t)nq * slots : 0;
-    if (int rc = ensure_marg(ctx, par_b + quant_b + hist_b)) return rc;
-    QuantPar *dpar = reinterpret_cast<QuantPar *>(ctx->marg);
-    double *dquant = reinterpret_cast<double *>(static_cast<char *>(ctx->marg) + par_b);
-    unsigned long long *dhist = reinterpret_cast<unsigned long long *>(static_cast<char *>(ctx->marg) + par_b + quant_b);
+    if (int rc = grow(ctx, ctx->marg, par_b + quant_b + hist_b)) return rc;
+    QuantPar *dpar = ctx->marg.as<QuantPar>();
+    double *dquant = reinterpret_cast<double *>(ctx->marg.as<char>() + par_b);
+    unsigned long long *dhist = reinterpret_cast<unsigned long long *>(ctx->marg.as<char>() + par_b + quant_b);
     Timer *tm = ctx->timer.on ? &ctx->timer : nullptr;
     if (nprob > 0) {
         ctx->marg_par_h.resize(par_b);  // (outlives the copy: the caller synchronises before returning)
@@ -327,8 +317,8 @@ extern "C" int td_history_zeta_hist(td_ctx *ctx, td_history *const *hs, int64_t 
     const size_t hist_b = sizeof(int64_t) * (size_t)(nbins + 3);
     TD_HIP(ctx, hipSetDevice(ctx->device));
     servers_quiesce(nullptr);
-    if (int rc = ensure_marg(ctx, hist_b)) return rc;
-    unsigned long long *dhist = static_cast<unsigned long long *>(ctx->marg);
+    if (int rc = grow(ctx, ctx->marg, hist_b)) return rc;
+    unsigned long long *dhist = ctx->marg.as<unsigned long long>();
     TD_HIP(ctx, hipMemsetAsync(dhist, 0, hist_b, ctx->stream));
     Timer *tm = ctx->timer.on ? &ctx->timer : nullptr;
     int64_t pos = 0;

@@ -28,7 +28,4 @@ struct PredPlan {
 bool predict_plan(int64_t nmodels, int64_t n, const int64_t *ray_points, int64_t budget, int64_t forced_points,
                   int64_t forced_chunk, PredPlan *plan);
 
-// td_destroy: the predictive workspace of a context
-void predict_free(td_ctx *ctx);
-
 }  // namespace tdstar

@@ -25,6 +25,7 @@
 
 #include "convergence.h"
 #include "ctx.h"
+#include "ensemble.h"
 #include "history.h"
 #include "marginals.h"
 #include "predict.h"
@@ -128,16 +129,6 @@ __global__ __launch_bounds__(64) void k_pred_chi2(const double *__restrict__ ptS
     phi[m] = C;
 }
 
-int grow_pred(td_ctx *ctx, size_t bytes) {
-    if (bytes <= ctx->pred_cap) return TD_OK;
-    if (ctx->pred) (void)hipFree(ctx->pred);
-    ctx->pred = nullptr;
-    ctx->pred_cap = 0;
-    TD_HIP(ctx, hipMalloc(&ctx->pred, bytes));
-    ctx->pred_cap = bytes;
-    return TD_OK;
-}
-
 // the checks of both entry points that need no context and no HIP call
 int predict_check(td_ctx *ctx, const td_predict *out, const char *who) {
     const std::string w(who);
@@ -152,11 +143,10 @@ int predict_check(td_ctx *ctx, const td_predict *out, const char *who) {
     return TD_OK;
 }
 
-// Both entry points (volume_build's arguments); every argument has been checked.
-int predict_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *cell_off, const double *xCell,
-                 const double *yCell, const double *zCell, const double *zeta, const std::vector<td_history *> *segs,
-                 int64_t nchains, const int64_t *chain_len, const td_predict *out) {
+// Both entry points; E and out have been checked (ensemble.h, predict_check).
+int predict_core(td_ctx *ctx, const char *who, const Ensemble &E, const td_predict *out) {
     const std::string w(who);
+    const int64_t nmodels = E.nmodels;
     const int64_t n = ctx->g.n;
     const std::vector<int> &roff = ctx->ray_off_host;
     std::vector<int64_t> ray_points((size_t)n);
@@ -172,7 +162,7 @@ int predict_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *c
     TD_HIP(ctx, hipSetDevice(ctx->device));
     servers_quiesce(nullptr);
     VolSearch S;
-    if (int rc = volume_build(ctx, who, nmodels, cell_off, xCell, yCell, zCell, zeta, segs, &S)) return rc;
+    if (int rc = volume_build(ctx, who, E, &S)) return rc;
     hipStream_t s = ctx->stream;
     Timer *tm = ctx->timer.on ? &ctx->timer : nullptr;
     const auto &g = ctx->g;
@@ -182,8 +172,8 @@ int predict_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *c
     const bool gather = stats && sp.nodes < n;
     const int nprob = out->marg ? (int)out->marg->nprob : 0;
     // ctx->pred: ptS [nmodels][n] | phi [nmodels] | mean, std [n]
-    if (int rc = grow_pred(ctx, sizeof(double) * ((size_t)nmodels * (size_t)n + (size_t)nmodels + 2 * (size_t)n))) return rc;
-    double *dptS = static_cast<double *>(ctx->pred), *dphi = dptS + nmodels * n, *dm = dphi + nmodels, *dsd = dm + n;
+    if (int rc = grow(ctx, ctx->pred, sizeof(double) * ((size_t)nmodels * (size_t)n + (size_t)nmodels + 2 * (size_t)n))) return rc;
+    double *dptS = ctx->pred.as<double>(), *dphi = dptS + nmodels * n, *dm = dphi + nmodels, *dsd = dm + n;
     // ctx->raster: the slab's points [3][points] | V_slab [chunk][points] | a gathered slab of ptS
     int64_t maxpts = 0;
     for (size_t k = 0; k + 1 < plan.edges.size(); ++k)
@@ -191,7 +181,7 @@ int predict_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *c
     const size_t n_sweep = (size_t)maxpts * (3 + (size_t)plan.chunk), n_gather = gather ? (size_t)nmodels * (size_t)sp.nodes : 0;
     if (int rc = raster_reserve(ctx, std::max<size_t>(n_sweep + n_gather, 1), gather ? (size_t)nprob * (size_t)sp.nodes : 0))
         return rc;
-    double *dq = ctx->raster, *dv = dq + 3 * maxpts, *dg = ctx->raster + n_sweep;
+    double *dq = ctx->raster.as<double>(), *dv = dq + 3 * maxpts, *dg = dq + n_sweep;
     int64_t brute_pairs = 0;
     for (size_t k = 0; k + 1 < plan.edges.size(); ++k) {
         const int64_t r0 = plan.edges[k], nr = plan.edges[k + 1] - r0;
@@ -236,7 +226,8 @@ int predict_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *c
     }
     if (out->ptS_out)
         TD_HIP(ctx, hipMemcpyAsync(out->ptS_out, dptS, sizeof(double) * (size_t)nmodels * (size_t)n, hipMemcpyDeviceToHost, s));
-    double *hquant = ctx->h_raster;
+    // a gathered slab's quantile rows go through the pinned block
+    const SlabWant want{n, out->mean_out, out->std_out, nullptr, out->marg, out->conv};
     for (int64_t q0 = 0; stats && q0 < n; q0 += sp.nodes) {
         const int64_t ns = std::min(sp.nodes, n - q0);
         const double *vals = dptS;
@@ -245,36 +236,10 @@ int predict_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *c
                                          sizeof(double) * (size_t)ns, (size_t)nmodels, hipMemcpyDeviceToDevice, s));
             vals = dg;
         }
-        if (out->mean_out) {
-            TD_HIP(ctx, launch_raster_stats(vals, (int)nmodels, (int)ns, dm, dsd, s));
-            TD_HIP(ctx, hipMemcpyAsync(out->mean_out + q0, dm, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, s));
-            TD_HIP(ctx, hipMemcpyAsync(out->std_out + q0, dsd, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, s));
-        }
-        if (out->marg) {  // hist_out is contiguous per ray; a gathered slab's quantile rows go through the pinned block
-            td_marginals mw = *out->marg;
-            if (gather) mw.quant_out = nprob > 0 ? hquant : nullptr;
-            mw.hist_out = mw.nbins > 0 ? out->marg->hist_out + q0 * (mw.nbins + 3) : nullptr;
-            if (int rc = marginals_run(ctx, vals, nmodels, ns, &mw)) return rc;
-        }
-        if (out->conv) {
-            td_convergence cw = *out->conv;
-            if (cw.rhat_out) cw.rhat_out += q0;
-            if (cw.ess_out) cw.ess_out += q0;
-            if (cw.lags_out) cw.lags_out += q0;
-            if (int rc = convergence_run(ctx, vals, nmodels, ns, nchains, chain_len, &cw)) return rc;
-        }
-        if (gather) {
-            TD_HIP(ctx, hipStreamSynchronize(s));  // the pinned block is filled again by the next slab
-            for (int p = 0; p < nprob; ++p)
-                std::memcpy(out->marg->quant_out + (int64_t)p * n + q0, hquant + (int64_t)p * ns, sizeof(double) * (size_t)ns);
-        }
+        if (int rc = slab_statistics(ctx, E, want, vals, q0, ns, dm, dsd, gather, ctx->h_raster.as<double>())) return rc;
     }
     TD_HIP(ctx, hipStreamSynchronize(s));
-    unsigned long long cnt[4] = {0, 0, 0, 0};  // (tdt_volume_counters: the last call's, this one's sweeps too)
-    TD_HIP(ctx, hipMemcpy(cnt, S.counters, sizeof cnt, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 3; ++k) ctx->vol_counters[k] = S.grid && !ctx->vol_counting ? -1 : (int64_t)cnt[k];
-    ctx->vol_counters[3] = brute_pairs;
-    return TD_OK;
+    return volume_counters_finish(ctx, S, brute_pairs);  // (tdt_volume_counters: the last call's, this one's sweeps too)
 }
 
 }  // namespace
@@ -306,12 +271,6 @@ bool predict_plan(int64_t nmodels, int64_t n, const int64_t *ray_points, int64_t
     return true;
 }
 
-void predict_free(td_ctx *ctx) {
-    if (ctx->pred) (void)hipFree(ctx->pred);
-    ctx->pred = nullptr;
-    ctx->pred_cap = 0;
-}
-
 }  // namespace tdstar
 
 using namespace tdstar;
@@ -321,48 +280,28 @@ extern "C" int td_rasterize_predict(td_ctx *ctx, int64_t nmodels, const int64_t 
                                     const int64_t *chain_len, const td_predict *out) {
     const char *who = "td_rasterize_predict";
     if (int rc = predict_check(ctx, out, who)) return rc;
-    const std::string w(who);
-    if (nmodels >= 1 && cell_off) {
-        const int64_t total = cell_off[nmodels];
-        if (cell_off[0] != 0 || total < 0 || (total > 0 && (!xCell || !yCell || !zCell || !zeta)))
-            return set_err(ctx, TD_ERR_ARG, w + ": bad cell offsets or arrays");
-        for (int64_t k = 0; k < nmodels; ++k)
-            if (cell_off[k + 1] < cell_off[k]) return set_err(ctx, TD_ERR_ARG, w + ": offsets not monotone");
-    }
+    const bool given = nmodels >= 1 && cell_off;  // (the chains are checked before the refusal of no models)
+    if (given)  // models and offsets are there: the arrays' refusals come before the chains'
+        if (int rc = ensemble_check_arrays(ctx, who, nmodels, cell_off, xCell, yCell, zCell, zeta)) return rc;
     if (out->conv)
         if (int rc = conv_check_chains(ctx, nchains, chain_len, std::max<int64_t>(nmodels, 0), who)) return rc;
-    if (nmodels < 1 || !cell_off) return set_err(ctx, TD_ERR_ARG, w + ": need nmodels >= 1 and cell_off");
-    if (!ctx) return set_err(nullptr, TD_ERR_ARG, w + ": ctx is NULL");
-    return predict_core(ctx, who, nmodels, cell_off, xCell, yCell, zCell, zeta, nullptr, nchains, chain_len, out);
+    // no models or no offsets: refused after the chains, in ensemble_check_arrays' words
+    if (!given) return ensemble_check_arrays(ctx, who, nmodels, cell_off, xCell, yCell, zCell, zeta);
+    if (!ctx) return set_err(nullptr, TD_ERR_ARG, std::string(who) + ": ctx is NULL");
+    return predict_core(ctx, who, Ensemble(nmodels, cell_off, xCell, yCell, zCell, zeta, nchains, chain_len), out);
 }
 
 extern "C" int td_history_predict(td_ctx *ctx, td_history *const *hs, int64_t nh, const td_predict *out) {
     const char *who = "td_history_predict";
     if (int rc = predict_check(ctx, out, who)) return rc;
-    const std::string w(who);
-    std::vector<td_history *> segs;
-    std::vector<int64_t> off(1, 0), lens;  // the concatenation's prefix, from the histories' host mirrors
-    for (int64_t i = 0; hs && i < nh; ++i) {
-        td_history *h = hs[i];
-        if (!h) return set_err(ctx, TD_ERR_ARG, w + ": a history is NULL");
-        const int64_t base = off.back();
-        for (int64_t k = 1; k <= h->samples; ++k) off.push_back(base + h->off[(size_t)k]);
-        if (h->samples > 0) {  // (one without samples is skipped)
-            segs.push_back(h);
-            lens.push_back(h->samples);
-        }
-    }
-    const int64_t nmodels = (int64_t)off.size() - 1;
-    if (out->conv && nmodels > 0)
-        if (int rc = conv_check_chains(ctx, (int64_t)lens.size(), lens.data(), nmodels, who)) return rc;
-    if (nmodels < 1) return set_err(ctx, TD_ERR_ARG, w + ": the histories hold no sample");
-    if (!ctx) return set_err(nullptr, TD_ERR_ARG, w + ": ctx is NULL");
-    for (td_history *h : segs) {  // any context's history on this device: only its cells and offsets are read
-        if (h->ctx->device != ctx->device) return set_err(ctx, TD_ERR_ARG, w + ": every history must live on the context's device");
-        if (h->ctx != ctx) TD_HIP(ctx, hipStreamSynchronize(h->ctx->stream));  // (what recorded it has ended)
-    }
-    return predict_core(ctx, who, nmodels, off.data(), nullptr, nullptr, nullptr, nullptr, &segs, (int64_t)lens.size(),
-                        lens.data(), out);
+    Ensemble E;
+    if (int rc = ensemble_from_histories(ctx, who, hs, nh, HistoryRule::SameDevice, &E)) return rc;
+    if (out->conv)
+        if (int rc = conv_check_chains(ctx, E.nchains, E.chain_len, E.nmodels, who)) return rc;
+    if (!ctx) return set_err(nullptr, TD_ERR_ARG, std::string(who) + ": ctx is NULL");
+    if (int rc = ensemble_check_device(ctx, who, E)) return rc;
+    if (int rc = ensemble_sync_foreign(ctx, E)) return rc;
+    return predict_core(ctx, who, E, out);
 }
 
 extern "C" int tdt_predict_plan(int64_t nmodels, int64_t n, const int64_t *ray_points, int64_t budget,

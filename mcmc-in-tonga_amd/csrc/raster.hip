@@ -20,6 +20,7 @@
 
 #include "convergence.h"
 #include "ctx.h"
+#include "ensemble.h"
 #include "history.h"
 #include "marginals.h"
 #include "volume.h"
@@ -218,21 +219,8 @@ __global__ __launch_bounds__(256) void k_raster_stats(const double *__restrict__
 using namespace tdstar;
 
 int tdstar::raster_reserve(td_ctx *ctx, size_t nd, size_t nh) {
-    if (nd > ctx->raster_cap) {
-        if (ctx->raster) (void)hipFree(ctx->raster);
-        ctx->raster = nullptr;
-        ctx->raster_cap = 0;
-        TD_HIP(ctx, hipMalloc(&ctx->raster, sizeof(double) * nd));
-        ctx->raster_cap = nd;
-    }
-    if (nh > ctx->h_raster_cap) {
-        if (ctx->h_raster) (void)hipHostFree(ctx->h_raster);
-        ctx->h_raster = nullptr;
-        ctx->h_raster_cap = 0;
-        TD_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_raster), sizeof(double) * nh, hipHostMallocDefault));
-        ctx->h_raster_cap = nh;
-    }
-    return TD_OK;
+    if (int rc = grow(ctx, ctx->raster, sizeof(double) * nd)) return rc;
+    return grow(ctx, ctx->h_raster, sizeof(double) * nh);
 }
 
 // volume.hip sweeps a slab of nodes with the same two kernels (volume.h)
@@ -267,31 +255,38 @@ bool raster_batched(int64_t nmodels, int64_t total, int64_t nq) {
            (int64_t)kXcds * ((nmodels + kXcds - 1) / kXcds) * ((nq + kRasterNodes - 1) / kRasterNodes) <= INT32_MAX;
 }
 
-// td_rasterize.  segs == nullptr: the cells are the host arrays.  Else (td_history_rasterize, the batched
-// launch only) they are in device memory already: histories' packed samples, segment after segment,
-// copied device to device behind the queries; cell_off is the concatenation's (host) prefix.
-// want (td_rasterize_marginals / td_history_marginals, else nullptr): quantiles and histograms of the
-// value matrix as well (marginals.hip), already checked by marg_check_want.
-// conv (td_rasterize_convergence / td_history_convergence, else nullptr): R-hat and ESS of the value
-// matrix's columns as well (convergence.hip), already checked by conv_check_want / conv_check_chains.
-int rasterize_core(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const double *xCell, const double *yCell,
-                   const double *zCell, const double *zeta, const std::vector<td_history *> *segs, const double *qx,
-                   const double *qy, const double *qz, int64_t nq, double *mean_out, double *std_out,
-                   double *values_out, const td_marginals *want = nullptr, const ConvRequest *conv = nullptr) {
-    if (!ctx) return set_err(nullptr, TD_ERR_ARG, "td_rasterize: ctx is NULL");
-    if (nmodels < 1 || !cell_off || nq < 0 || (nq > 0 && (!qx || !qy || !qz || !mean_out || !std_out)))
+// The request of every section entry point: the nodes, the caller's outputs, and what is computed of the
+// value matrix besides its mean and standard deviation
+struct SectionRequest {
+    const double *qx, *qy, *qz;
+    int64_t nq;
+    double *mean_out, *std_out, *values_out;
+    const td_marginals *want;    // td_rasterize_marginals / td_history_marginals, else nullptr
+    const td_convergence *conv;  // td_rasterize_convergence / td_history_convergence, else nullptr
+};
+
+// (the td_rasterize wording, whichever of them was called)
+int raster_check_request(td_ctx *ctx, const SectionRequest &r) {
+    if (r.nq < 0 || (r.nq > 0 && (!r.qx || !r.qy || !r.qz || !r.mean_out || !r.std_out)))
         return set_err(ctx, TD_ERR_ARG, "td_rasterize: bad arguments");
-    const int64_t total = cell_off[nmodels];
-    if (cell_off[0] != 0 || total < 0 || (!segs && total > 0 && (!xCell || !yCell || !zCell || !zeta)))
-        return set_err(ctx, TD_ERR_ARG, "td_rasterize: bad cell offsets or arrays");
-    for (int64_t k = 0; k < nmodels; ++k)
-        if (cell_off[k + 1] < cell_off[k]) return set_err(ctx, TD_ERR_ARG, "td_rasterize: offsets not monotone");
+    return TD_OK;
+}
+
+// The section entry points; E and the request have been checked (ensemble.h, raster_check_request).  Host
+// arrays are packed into the pinned block behind the queries and reach the device in one copy; E.segs
+// (td_history_rasterize, the batched launch only) are copied device to device behind the queries.
+// r.want: quantiles and histograms of the value matrix as well (marginals.hip), already checked by
+// marg_check_want.
+// r.conv: R-hat and ESS of the value matrix's columns over E's chains as well (convergence.hip), already
+// checked by conv_check_want / conv_check_chains.
+int rasterize_core(td_ctx *ctx, const Ensemble &E, const SectionRequest &r) {
+    const int64_t nmodels = E.nmodels, total = E.total(), *cell_off = E.cell_off, nq = r.nq;
     if (nq == 0) return TD_OK;
     if (nq > 0x7fffffff / std::max<int64_t>(nmodels, 1) || total > 0x7fffffff)
         return set_err(ctx, TD_ERR_ARG, "td_rasterize: too large");
     // marginals_run's own refusal, made here before anything is issued: there the search kernels and the
     // copies into mean_out / std_out are already under way, and the call would return while they run
-    if (int rc = marg_check_models(ctx, want, nmodels)) return rc;
+    if (int rc = marg_check_models(ctx, r.want, nmodels)) return rc;
     TD_HIP(ctx, hipSetDevice(ctx->device));
     servers_quiesce(nullptr);
     // one device block: queries (3 nq), all cells SoA (4 total), values (nmodels nq), mean, std (2 nq)
@@ -299,59 +294,31 @@ int rasterize_core(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const 
     const int64_t cs = std::max<int64_t>(total, 1);  // SoA stride of the cells
     // packed into a pinned staging block (reused across calls), then one DMA copy: pageable
     // copies of these sizes run at ~1 GB/s here
-    const size_t nh = 3 * (size_t)nq + (segs ? 0 : 4 * (size_t)cs);
+    const size_t nh = 3 * (size_t)nq + (E.segs ? 0 : 4 * (size_t)cs);
     if (int rc = raster_reserve(ctx, nd, nh)) return rc;
-    double *dq = ctx->raster, *dc = dq + 3 * nq, *dv = dc + 4 * cs, *dm = dv + nmodels * nq, *ds = dm + nq;
+    double *dq = ctx->raster.as<double>(), *dc = dq + 3 * nq, *dv = dc + 4 * cs, *dm = dv + nmodels * nq, *ds = dm + nq;
     TD_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the staging block may still feed a previous copy
-    double *h = ctx->h_raster;
-    std::memcpy(h, qx, sizeof(double) * (size_t)nq);
-    std::memcpy(h + nq, qy, sizeof(double) * (size_t)nq);
-    std::memcpy(h + 2 * nq, qz, sizeof(double) * (size_t)nq);
-    double *hc = h + 3 * nq;
-    if (total > 0 && !segs) {
-        std::memcpy(hc, xCell, sizeof(double) * (size_t)total);
-        std::memcpy(hc + cs, yCell, sizeof(double) * (size_t)total);
-        std::memcpy(hc + 2 * cs, zCell, sizeof(double) * (size_t)total);
-        std::memcpy(hc + 3 * cs, zeta, sizeof(double) * (size_t)total);
+    double *h = ctx->h_raster.as<double>(), *hc = h + 3 * nq;
+    pack_queries(ctx, r.qx, r.qy, r.qz, 0, nq);
+    if (total > 0 && !E.segs) {
+        std::memcpy(hc, E.x, sizeof(double) * (size_t)total);
+        std::memcpy(hc + cs, E.y, sizeof(double) * (size_t)total);
+        std::memcpy(hc + 2 * cs, E.z, sizeof(double) * (size_t)total);
+        std::memcpy(hc + 3 * cs, E.zeta, sizeof(double) * (size_t)total);
     }
     TD_HIP(ctx, hipMemcpyAsync(dq, h, sizeof(double) * nh, hipMemcpyHostToDevice, ctx->stream));
-    if (segs) {  // each history's packed samples behind the ones before, component by component
-        int64_t pos = 0;
-        for (const td_history *hh : *segs) {
-            const int64_t cnt = hh->off[(size_t)hh->samples];
-            for (int comp = 0; comp < 4 && cnt > 0; ++comp)
-                TD_HIP(ctx, hipMemcpyAsync(dc + comp * cs + pos, hh->d.cells + comp * hh->d.stride,
-                                           sizeof(double) * (size_t)cnt, hipMemcpyDeviceToDevice, ctx->stream));
-            pos += cnt;
-        }
-    }
-    if (nq > ctx->raster_i_cap) {  // nearest-cell indices (not returned)
-        if (ctx->raster_i) (void)hipFree(ctx->raster_i);
-        ctx->raster_i = nullptr;
-        ctx->raster_i_cap = 0;
-        TD_HIP(ctx, hipMalloc(&ctx->raster_i, sizeof(int) * (size_t)nq));
-        ctx->raster_i_cap = nq;
-    }
+    if (E.segs)
+        if (int rc = ensemble_copy_segments(ctx, E, dc, cs, ctx->stream)) return rc;
+    if (int rc = grow(ctx, ctx->raster_i, sizeof(int) * (size_t)nq)) return rc;  // nearest-cell indices (not returned)
     Timer *tm = ctx->timer.on ? &ctx->timer : nullptr;
     const bool batched = raster_batched(nmodels, total, nq);
-    if (segs && !batched) return set_err(ctx, TD_ERR_ARG, "td_history_rasterize: internal: per-model path");
+    if (E.segs && !batched) return set_err(ctx, TD_ERR_ARG, "td_history_rasterize: internal: per-model path");
     if (batched) {
-        if (nmodels + 1 > ctx->raster_off_cap) {
-            if (ctx->raster_off) (void)hipFree(ctx->raster_off);
-            ctx->raster_off = nullptr;
-            ctx->raster_off_cap = 0;
-            TD_HIP(ctx, hipMalloc(&ctx->raster_off, sizeof(int64_t) * (size_t)(nmodels + 1)));
-            ctx->raster_off_cap = nmodels + 1;
-        }
-        TD_HIP(ctx, hipMemcpyAsync(ctx->raster_off, cell_off, sizeof(int64_t) * (size_t)(nmodels + 1),
-                                   hipMemcpyHostToDevice, ctx->stream));
-        hipEvent_t t0 = tm ? tm->begin(ctx->stream) : nullptr;
-        const int nchunks = (int)((nq + kRasterNodes - 1) / kRasterNodes);
-        const int64_t blocks = (int64_t)kXcds * ((nmodels + kXcds - 1) / kXcds) * nchunks;
-        hipLaunchKernelGGL(k_raster_brute, dim3((unsigned)blocks), dim3(kRasterThreads), 0, ctx->stream,
-                           ctx->raster_off, dc, cs, dq, (int)nq, (int)nmodels, nchunks, dv);
-        if (tm) tm->end("raster_brute", t0, ctx->stream);
-        TD_HIP(ctx, hipGetLastError());
+        if (int rc = grow(ctx, ctx->raster_off, sizeof(int64_t) * (size_t)(nmodels + 1))) return rc;
+        int64_t *doff = ctx->raster_off.as<int64_t>();
+        TD_HIP(ctx, hipMemcpyAsync(doff, cell_off, sizeof(int64_t) * (size_t)(nmodels + 1), hipMemcpyHostToDevice,
+                                   ctx->stream));
+        TD_HIP(ctx, launch_raster_brute(doff, dc, cs, dq, (int)nq, (int)nmodels, dv, ctx->stream, tm));
     }
     for (int64_t k = 0; k < (batched ? 0 : nmodels); ++k) {
         const int64_t a = cell_off[k], nc = cell_off[k + 1] - a;
@@ -359,7 +326,7 @@ int rasterize_core(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const 
         hipError_t e;
         if (nc >= kGridMinCells && ctx->nn_method != 1) {
             double lo[3], hi[3];
-            const double *src[3] = {xCell + a, yCell + a, zCell + a};
+            const double *src[3] = {E.x + a, E.y + a, E.z + a};
             for (int d = 0; d < 3; ++d) {
                 double l = HUGE_VAL, u = -HUGE_VAL;
                 for (int64_t i = 0; i < nc; ++i) {
@@ -371,27 +338,59 @@ int rasterize_core(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const 
             }
             const CellGrid G = make_cell_grid(lo, hi, (double)nc / 2.0, 4096, kGridMaxBuckets);
             e = launch_nearest_grid(dq, dq + nq, dq + 2 * nq, nq, 1, 1, dc + a, cs, nc, G, ctx->nn, ctx->num_cus,
-                                    ctx->raster_i, nullptr, out, ctx->stream, tm);
+                                    ctx->raster_i.as<int>(), nullptr, out, ctx->stream, tm);
         } else {
             e = launch_nearest(dq, dq + nq, dq + 2 * nq, nq, 1, 1, dc + a, cs, nc, ctx->nn, ctx->num_cus,
-                               ctx->raster_i, nullptr, out, ctx->stream, tm);
+                               ctx->raster_i.as<int>(), nullptr, out, ctx->stream, tm);
         }
         if (e != hipSuccess) return hip_err(ctx, e, "td_rasterize: nearest kernels");
     }
-    hipLaunchKernelGGL(k_raster_stats, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream, dv,
-                       (int)nmodels, (int)nq, dm, ds);
-    TD_HIP(ctx, hipGetLastError());
-    TD_HIP(ctx, hipMemcpyAsync(mean_out, dm, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-    TD_HIP(ctx, hipMemcpyAsync(std_out, ds, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
-    if (want)
-        if (int rc = marginals_run(ctx, dv, nmodels, nq, want)) return rc;
-    if (conv)
-        if (int rc = convergence_run(ctx, dv, nmodels, nq, conv->nchains, conv->chain_len, conv->want)) return rc;
-    if (values_out)
-        TD_HIP(ctx, hipMemcpyAsync(values_out, dv, sizeof(double) * (size_t)nq * nmodels, hipMemcpyDeviceToHost,
+    TD_HIP(ctx, launch_raster_stats(dv, (int)nmodels, (int)nq, dm, ds, ctx->stream));
+    TD_HIP(ctx, hipMemcpyAsync(r.mean_out, dm, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    TD_HIP(ctx, hipMemcpyAsync(r.std_out, ds, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+    if (r.want)
+        if (int rc = marginals_run(ctx, dv, nmodels, nq, r.want)) return rc;
+    if (r.conv)
+        if (int rc = convergence_run(ctx, dv, nmodels, nq, E.nchains, E.chain_len, r.conv)) return rc;
+    if (r.values_out)
+        TD_HIP(ctx, hipMemcpyAsync(r.values_out, dv, sizeof(double) * (size_t)nq * nmodels, hipMemcpyDeviceToHost,
                                    ctx->stream));
     TD_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return TD_OK;
+}
+
+// td_rasterize, td_rasterize_marginals and td_rasterize_convergence; E holds the caller's arguments, unchecked
+int rasterize_arrays(td_ctx *ctx, const Ensemble &E, const SectionRequest &r) {
+    if (!ctx) return set_err(nullptr, TD_ERR_ARG, "td_rasterize: ctx is NULL");
+    if (E.nmodels < 1 || !E.cell_off) return set_err(ctx, TD_ERR_ARG, "td_rasterize: bad arguments");
+    if (int rc = raster_check_request(ctx, r)) return rc;
+    if (int rc = ensemble_check_arrays(ctx, "td_rasterize", E.nmodels, E.cell_off, E.x, E.y, E.z, E.zeta)) return rc;
+    return rasterize_core(ctx, E, r);
+}
+
+// td_history_rasterize, td_history_marginals and td_history_convergence (one history with samples = one chain)
+int history_rasterize(td_ctx *ctx, td_history *const *hs, int64_t nh, const SectionRequest &r) {
+    Ensemble E;
+    if (int rc = ensemble_from_histories(ctx, "td_history_rasterize", hs, nh, HistoryRule::SameContext, &E)) return rc;
+    if (r.conv)
+        if (int rc = conv_check_chains(ctx, E.nchains, E.chain_len, E.nmodels, "td_history_convergence")) return rc;
+    if (int rc = raster_check_request(ctx, r)) return rc;
+    if (raster_batched(E.nmodels, E.total(), r.nq)) return rasterize_core(ctx, E, r);
+    // the per-model search computes each model's bounding box on the host: fetch the cells
+    const size_t total = (size_t)std::max<int64_t>(E.total(), 1);
+    std::vector<double> c(4 * total);
+    size_t pos = 0;
+    for (td_history *h : *E.segs) {
+        const int64_t cnt = h->off[(size_t)h->samples];
+        int rc = td_history_read(h, 0, h->samples, nullptr, c.data() + pos, c.data() + total + pos,
+                                 c.data() + 2 * total + pos, c.data() + 3 * total + pos, cnt, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr);
+        if (rc) return rc;
+        pos += (size_t)cnt;
+    }
+    const Ensemble F(E.nmodels, E.cell_off, c.data(), c.data() + total, c.data() + 2 * total, c.data() + 3 * total,
+                     E.nchains, E.chain_len);
+    return rasterize_core(ctx, F, r);
 }
 
 }  // namespace
@@ -400,65 +399,14 @@ extern "C" int td_rasterize(td_ctx *ctx, int64_t nmodels, const int64_t *cell_of
                             const double *yCell, const double *zCell, const double *zeta, const double *qx,
                             const double *qy, const double *qz, int64_t nq, double *mean_out, double *std_out,
                             double *values_out) {
-    return rasterize_core(ctx, nmodels, cell_off, xCell, yCell, zCell, zeta, nullptr, qx, qy, qz, nq, mean_out,
-                          std_out, values_out);
+    return rasterize_arrays(ctx, Ensemble(nmodels, cell_off, xCell, yCell, zCell, zeta),
+                            {qx, qy, qz, nq, mean_out, std_out, values_out, nullptr, nullptr});
 }
-
-namespace {
-
-// td_history_rasterize, td_history_marginals (want non-null) and td_history_convergence (cwant
-// non-null: one history with samples = one chain)
-int history_rasterize(td_ctx *ctx, td_history *const *hs, int64_t nh, const double *qx, const double *qy,
-                      const double *qz, int64_t nq, double *mean_out, double *std_out, double *values_out,
-                      const td_marginals *want, const td_convergence *cwant = nullptr) {
-    if (!ctx) return set_err(nullptr, TD_ERR_ARG, "td_history_rasterize: ctx is NULL");
-    if (!hs || nh < 1) return set_err(ctx, TD_ERR_ARG, "td_history_rasterize: no history");
-    std::vector<td_history *> segs;
-    std::vector<int64_t> off(1, 0);  // the concatenation's prefix, from the histories' host mirrors
-    for (int64_t i = 0; i < nh; ++i) {
-        td_history *h = hs[i];
-        if (!h || h->ctx != ctx)
-            return set_err(ctx, TD_ERR_ARG, "td_history_rasterize: every history must be non-NULL and of this context");
-        const int64_t base = off.back();
-        for (int64_t k = 1; k <= h->samples; ++k) off.push_back(base + h->off[(size_t)k]);
-        if (h->samples > 0) segs.push_back(h);
-    }
-    const int64_t nmodels = (int64_t)off.size() - 1;
-    if (nmodels < 1) return set_err(ctx, TD_ERR_ARG, "td_history_rasterize: the histories hold no sample");
-    std::vector<int64_t> lens;
-    ConvRequest creq{0, nullptr, cwant};
-    if (cwant) {
-        for (const td_history *h : segs) lens.push_back(h->samples);
-        creq.nchains = (int64_t)lens.size();
-        creq.chain_len = lens.data();
-        if (int rc = conv_check_chains(ctx, creq.nchains, creq.chain_len, nmodels, "td_history_convergence")) return rc;
-    }
-    const ConvRequest *conv = cwant ? &creq : nullptr;
-    if (raster_batched(nmodels, off.back(), nq))
-        return rasterize_core(ctx, nmodels, off.data(), nullptr, nullptr, nullptr, nullptr, &segs, qx, qy, qz, nq,
-                              mean_out, std_out, values_out, want, conv);
-    // the per-model search computes each model's bounding box on the host: fetch the cells
-    const size_t total = (size_t)std::max<int64_t>(off.back(), 1);
-    std::vector<double> c(4 * total);
-    size_t pos = 0;
-    for (td_history *h : segs) {
-        const int64_t cnt = h->off[(size_t)h->samples];
-        int rc = td_history_read(h, 0, h->samples, nullptr, c.data() + pos, c.data() + total + pos,
-                                 c.data() + 2 * total + pos, c.data() + 3 * total + pos, cnt, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr);
-        if (rc) return rc;
-        pos += (size_t)cnt;
-    }
-    return rasterize_core(ctx, nmodels, off.data(), c.data(), c.data() + total, c.data() + 2 * total,
-                          c.data() + 3 * total, nullptr, qx, qy, qz, nq, mean_out, std_out, values_out, want, conv);
-}
-
-}  // namespace
 
 extern "C" int td_history_rasterize(td_ctx *ctx, td_history *const *hs, int64_t nh, const double *qx,
                                     const double *qy, const double *qz, int64_t nq, double *mean_out,
                                     double *std_out, double *values_out) {
-    return history_rasterize(ctx, hs, nh, qx, qy, qz, nq, mean_out, std_out, values_out, nullptr);
+    return history_rasterize(ctx, hs, nh, {qx, qy, qz, nq, mean_out, std_out, values_out, nullptr, nullptr});
 }
 
 extern "C" int td_rasterize_marginals(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const double *xCell,
@@ -466,15 +414,15 @@ extern "C" int td_rasterize_marginals(td_ctx *ctx, int64_t nmodels, const int64_
                                       const double *qy, const double *qz, int64_t nq, double *mean_out,
                                       double *std_out, const td_marginals *want) {
     if (int rc = marg_check_want(ctx, want, "td_rasterize_marginals")) return rc;
-    return rasterize_core(ctx, nmodels, cell_off, xCell, yCell, zCell, zeta, nullptr, qx, qy, qz, nq, mean_out,
-                          std_out, nullptr, want);
+    return rasterize_arrays(ctx, Ensemble(nmodels, cell_off, xCell, yCell, zCell, zeta),
+                            {qx, qy, qz, nq, mean_out, std_out, nullptr, want, nullptr});
 }
 
 extern "C" int td_history_marginals(td_ctx *ctx, td_history *const *hs, int64_t nh, const double *qx,
                                     const double *qy, const double *qz, int64_t nq, double *mean_out,
                                     double *std_out, const td_marginals *want) {
     if (int rc = marg_check_want(ctx, want, "td_history_marginals")) return rc;
-    return history_rasterize(ctx, hs, nh, qx, qy, qz, nq, mean_out, std_out, nullptr, want);
+    return history_rasterize(ctx, hs, nh, {qx, qy, qz, nq, mean_out, std_out, nullptr, want, nullptr});
 }
 
 extern "C" int td_rasterize_convergence(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const double *xCell,
@@ -484,14 +432,13 @@ extern "C" int td_rasterize_convergence(td_ctx *ctx, int64_t nmodels, const int6
                                         const td_convergence *want) {
     if (int rc = conv_check_want(ctx, want, "td_rasterize_convergence")) return rc;
     if (int rc = conv_check_chains(ctx, nchains, chain_len, nmodels, "td_rasterize_convergence")) return rc;
-    const ConvRequest conv{nchains, chain_len, want};
-    return rasterize_core(ctx, nmodels, cell_off, xCell, yCell, zCell, zeta, nullptr, qx, qy, qz, nq, mean_out,
-                          std_out, nullptr, nullptr, &conv);
+    return rasterize_arrays(ctx, Ensemble(nmodels, cell_off, xCell, yCell, zCell, zeta, nchains, chain_len),
+                            {qx, qy, qz, nq, mean_out, std_out, nullptr, nullptr, want});
 }
 
 extern "C" int td_history_convergence(td_ctx *ctx, td_history *const *hs, int64_t nh, const double *qx,
                                       const double *qy, const double *qz, int64_t nq, double *mean_out,
                                       double *std_out, const td_convergence *want) {
     if (int rc = conv_check_want(ctx, want, "td_history_convergence")) return rc;
-    return history_rasterize(ctx, hs, nh, qx, qy, qz, nq, mean_out, std_out, nullptr, nullptr, want);
+    return history_rasterize(ctx, hs, nh, {qx, qy, qz, nq, mean_out, std_out, nullptr, nullptr, want});
 }

@@ -7,9 +7,9 @@
 
 #include "ctx.h"
 
-struct td_history;
-
 namespace tdstar {
+
+struct Ensemble;  // ensemble.h
 
 constexpr int64_t kVolTile = 64;                         // a slab is a multiple of this many nodes
 constexpr int64_t kVolDefaultBudget = (int64_t)1 << 30;  // bytes of V_slab[nmodels][slab nodes]
@@ -49,16 +49,15 @@ struct VolSearch {
     std::vector<CellGrid> grids_host;        // what grids and boff were copied from
     std::vector<int64_t> boff_host;
 };
-// segs == nullptr: the cells are the host arrays; else the histories' packed samples (any context's, on
-// ctx's device), cell_off the concatenation's host prefix.  Every argument has been checked.
-int volume_build(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *cell_off, const double *xCell,
-                 const double *yCell, const double *zCell, const double *zeta, const std::vector<td_history *> *segs,
-                 VolSearch *out);
+// The host arrays reach the device in four copies from the caller's arrays, a history's samples device to
+// device (any context's, on ctx's device).
+int volume_build(td_ctx *ctx, const char *who, const Ensemble &E, VolSearch *out);
 // values[nm][ns] = the nearest cell's zeta of the models [m0, m0 + nm) at the device queries q = [3][ns],
 // ns >= 1 (timers vol_search / raster_brute)
 int volume_sweep(td_ctx *ctx, const VolSearch &S, int64_t m0, int64_t nm, const double *q, int64_t ns, double *values);
-
-// td_destroy: the volume workspaces of a context
-void volume_free(td_ctx *ctx);
+// The end of a call that swept S: tdt_volume_counters' numbers (brute_pairs: the pairs k_raster_brute took)
+int volume_counters_finish(td_ctx *ctx, const VolSearch &S, int64_t brute_pairs);
+// raster.hip: room for nd doubles in ctx->raster and nh doubles in the pinned ctx->h_raster
+int raster_reserve(td_ctx *ctx, size_t nd, size_t nh);
 
 }  // namespace tdstar

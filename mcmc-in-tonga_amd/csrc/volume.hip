@@ -32,6 +32,7 @@
 
 #include "convergence.h"
 #include "ctx.h"
+#include "ensemble.h"
 #include "history.h"
 #include "marginals.h"
 #include "volume.h"
@@ -261,16 +262,6 @@ __global__ __launch_bounds__(kVolThreads) void k_vol_search(const int64_t *__res
 
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-int grow_dev(td_ctx *ctx, void *&ptr, size_t &cap, size_t bytes) {
-    if (bytes <= cap) return TD_OK;
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    cap = 0;
-    TD_HIP(ctx, hipMalloc(&ptr, bytes));
-    cap = bytes;
-    return TD_OK;
-}
-
 // A model whose box is not finite (a cell at infinity, an extent that overflows): one bucket, no box
 // bound -- its search is the scan of that bucket, which is every cell.
 CellGrid one_bucket_grid() {
@@ -281,15 +272,12 @@ CellGrid one_bucket_grid() {
 
 }  // namespace
 
-// The search structure of td_rasterize_volume / td_history_volume and of the posterior predictive calls
-// (predict.hip), in ctx's volume workspaces: segs == nullptr: the cells are the host arrays; else they are
-// the histories' packed samples, copied device to device behind one another (cell_off is the
-// concatenation's host prefix).  Every argument has been checked.
-int volume_build(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *cell_off, const double *xCell,
-                 const double *yCell, const double *zCell, const double *zeta, const std::vector<td_history *> *segs,
-                 VolSearch *out) {
+// The search structure of the volume, predictive and covariance calls, in ctx's volume workspaces.  E has
+// been checked (ensemble.h).
+int volume_build(td_ctx *ctx, const char *who, const Ensemble &E, VolSearch *out) {
     const std::string w(who);
-    const int64_t total = cell_off[nmodels], cs = std::max<int64_t>(total, 1);
+    const int64_t nmodels = E.nmodels, *cell_off = E.cell_off;
+    const int64_t total = E.total(), cs = std::max<int64_t>(total, 1);
     if (nmodels > INT32_MAX - 64) return set_err(ctx, TD_ERR_ARG, w + ": too many models");
     for (int64_t k = 0; k < nmodels; ++k)
         if (cell_off[k + 1] - cell_off[k] > INT32_MAX) return set_err(ctx, TD_ERR_ARG, w + ": a model of too many cells");
@@ -301,8 +289,8 @@ int volume_build(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *c
     // the models: cells SoA | offsets | boxes | grids | bucket prefix | counters
     const size_t b_cells = up256(sizeof(double) * 4 * (size_t)cs), b_off = up256(sizeof(int64_t) * (size_t)(nmodels + 1)),
                  b_box = up256(sizeof(double) * 6 * (size_t)nmodels), b_grid = up256(sizeof(CellGrid) * (size_t)nmodels);
-    if (int rc = grow_dev(ctx, ctx->vol, ctx->vol_cap, b_cells + 2 * b_off + b_box + b_grid + 256)) return rc;
-    char *base = static_cast<char *>(ctx->vol);
+    if (int rc = grow(ctx, ctx->vol, b_cells + 2 * b_off + b_box + b_grid + 256)) return rc;
+    char *base = ctx->vol.as<char>();
     double *dc = reinterpret_cast<double *>(base);
     int64_t *doff = reinterpret_cast<int64_t *>(base + b_cells);
     double *dbox = reinterpret_cast<double *>(base + b_cells + b_off);
@@ -310,17 +298,10 @@ int volume_build(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *c
     int64_t *dboff = reinterpret_cast<int64_t *>(base + b_cells + b_off + b_box + b_grid);
     unsigned long long *dcount = reinterpret_cast<unsigned long long *>(base + b_cells + 2 * b_off + b_box + b_grid);
     TD_HIP(ctx, hipStreamSynchronize(s));
-    if (segs) {  // each history's packed samples behind the ones before, component by component
-        int64_t pos = 0;
-        for (const td_history *hh : *segs) {
-            const int64_t cnt = hh->off[(size_t)hh->samples];
-            for (int comp = 0; comp < 4 && cnt > 0; ++comp)
-                TD_HIP(ctx, hipMemcpyAsync(dc + comp * cs + pos, hh->d.cells + comp * hh->d.stride,
-                                           sizeof(double) * (size_t)cnt, hipMemcpyDeviceToDevice, s));
-            pos += cnt;
-        }
-    } else if (total > 0) {
-        const double *src[4] = {xCell, yCell, zCell, zeta};
+    if (E.segs) {
+        if (int rc = ensemble_copy_segments(ctx, E, dc, cs, s)) return rc;
+    } else if (total > 0) {  // (four copies from the caller's arrays; the sections pack theirs into the pinned block)
+        const double *src[4] = {E.x, E.y, E.z, E.zeta};
         for (int comp = 0; comp < 4; ++comp)
             TD_HIP(ctx, hipMemcpyAsync(dc + comp * cs, src[comp], sizeof(double) * (size_t)total, hipMemcpyHostToDevice, s));
     }
@@ -351,8 +332,8 @@ int volume_build(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *c
             boff[(size_t)m + 1] = boff[(size_t)m] + (int64_t)G.gx * G.gy * G.gz + 1;
         }
         const size_t nbp = (size_t)boff[(size_t)nmodels], b_start = up256(sizeof(int) * nbp);
-        if (int rc = grow_dev(ctx, ctx->vol_grid, ctx->vol_grid_cap, 2 * b_start + sizeof(BucketEntry) * (size_t)cs)) return rc;
-        char *gb = static_cast<char *>(ctx->vol_grid);
+        if (int rc = grow(ctx, ctx->vol_grid, 2 * b_start + sizeof(BucketEntry) * (size_t)cs)) return rc;
+        char *gb = ctx->vol_grid.as<char>();
         dstart = reinterpret_cast<int *>(gb);
         int *dcur = reinterpret_cast<int *>(gb + b_start);
         dent = reinterpret_cast<BucketEntry *>(gb + 2 * b_start);
@@ -399,63 +380,41 @@ int volume_sweep(td_ctx *ctx, const VolSearch &S, int64_t m0, int64_t nm, const 
     return TD_OK;
 }
 
+int volume_counters_finish(td_ctx *ctx, const VolSearch &S, int64_t brute_pairs) {
+    unsigned long long cnt[4] = {0, 0, 0, 0};
+    TD_HIP(ctx, hipMemcpy(cnt, S.counters, sizeof cnt, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 3; ++k) ctx->vol_counters[k] = S.grid && !ctx->vol_counting ? -1 : (int64_t)cnt[k];
+    ctx->vol_counters[3] = brute_pairs;
+    return TD_OK;
+}
+
 namespace {
 
-// td_rasterize_volume and td_history_volume (volume_build's arguments).
-int volume_core(td_ctx *ctx, const char *who, int64_t nmodels, const int64_t *cell_off, const double *xCell,
-                const double *yCell, const double *zCell, const double *zeta, const std::vector<td_history *> *segs,
-                int64_t nchains, const int64_t *chain_len, const td_volume *vol) {
+// td_rasterize_volume and td_history_volume; E and vol have been checked (ensemble.h, volume_check).
+int volume_core(td_ctx *ctx, const char *who, const Ensemble &E, const td_volume *vol) {
+    const int64_t nmodels = E.nmodels, nq = vol->nq;
+    if (nq == 0) return TD_OK;
     if (int rc = marg_check_models(ctx, vol->marg, nmodels)) return rc;  // (before anything is issued)
     VolSearch S;
-    if (int rc = volume_build(ctx, who, nmodels, cell_off, xCell, yCell, zCell, zeta, segs, &S)) return rc;
-    const int64_t nq = vol->nq;
-    const bool grid = S.grid;
-    hipStream_t s = ctx->stream;
-    unsigned long long *dcount = S.counters;
+    if (int rc = volume_build(ctx, who, E, &S)) return rc;
     // the slabs: queries [3][ns] | V_slab [nmodels][ns] | mean, std [ns]; pinned: queries | quantile rows
     const VolPlan plan = volume_plan(nmodels, nq, kVolDefaultBudget, ctx->vol_slab_nodes);
     const int64_t cap = std::min(plan.nodes, nq);
     const int nprob = vol->marg ? (int)vol->marg->nprob : 0;
     if (int rc = raster_reserve(ctx, (size_t)cap * (5 + (size_t)nmodels), (size_t)cap * (3 + (size_t)nprob))) return rc;
-    double *dq = ctx->raster, *dv = dq + 3 * cap, *dm = dv + nmodels * cap, *dsd = dm + cap;
-    double *h = ctx->h_raster, *hquant = h + 3 * cap;
+    double *dq = ctx->raster.as<double>(), *dv = dq + 3 * cap, *dm = dv + nmodels * cap, *dsd = dm + cap;
+    double *hquant = ctx->h_raster.as<double>() + 3 * cap;
+    const SlabWant want{nq, vol->mean_out, vol->std_out, vol->values_out, vol->marg, vol->conv};
     int64_t brute_pairs = 0;
     for (int64_t q0 = 0; q0 < nq; q0 += plan.nodes) {
         const int64_t ns = std::min(plan.nodes, nq - q0);
-        std::memcpy(h, vol->qx + q0, sizeof(double) * (size_t)ns);
-        std::memcpy(h + ns, vol->qy + q0, sizeof(double) * (size_t)ns);
-        std::memcpy(h + 2 * ns, vol->qz + q0, sizeof(double) * (size_t)ns);
-        TD_HIP(ctx, hipMemcpyAsync(dq, h, sizeof(double) * 3 * (size_t)ns, hipMemcpyHostToDevice, s));
+        if (int rc = stage_queries(ctx, vol->qx, vol->qy, vol->qz, q0, ns, dq)) return rc;
         if (int rc = volume_sweep(ctx, S, 0, nmodels, dq, ns, dv)) return rc;
-        if (!grid) brute_pairs += nmodels * ns;
-        TD_HIP(ctx, launch_raster_stats(dv, (int)nmodels, (int)ns, dm, dsd, s));
-        TD_HIP(ctx, hipMemcpyAsync(vol->mean_out + q0, dm, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, s));
-        TD_HIP(ctx, hipMemcpyAsync(vol->std_out + q0, dsd, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, s));
-        if (vol->marg) {  // hist_out is contiguous per node; the quantile rows go through the pinned block
-            td_marginals mw = *vol->marg;
-            mw.quant_out = nprob > 0 ? hquant : nullptr;
-            mw.hist_out = mw.nbins > 0 ? vol->marg->hist_out + q0 * (mw.nbins + 3) : nullptr;
-            if (int rc = marginals_run(ctx, dv, nmodels, ns, &mw)) return rc;
-        }
-        if (vol->conv) {
-            td_convergence cw = *vol->conv;
-            if (cw.rhat_out) cw.rhat_out += q0;
-            if (cw.ess_out) cw.ess_out += q0;
-            if (cw.lags_out) cw.lags_out += q0;
-            if (int rc = convergence_run(ctx, dv, nmodels, ns, nchains, chain_len, &cw)) return rc;
-        }
-        if (vol->values_out)
-            TD_HIP(ctx, hipMemcpy2DAsync(vol->values_out + q0, sizeof(double) * (size_t)nq, dv, sizeof(double) * (size_t)ns,
-                                         sizeof(double) * (size_t)ns, (size_t)nmodels, hipMemcpyDeviceToHost, s));
-        TD_HIP(ctx, hipStreamSynchronize(s));  // the pinned block is packed again for the next slab
-        for (int p = 0; p < nprob; ++p)
-            std::memcpy(vol->marg->quant_out + (int64_t)p * nq + q0, hquant + (int64_t)p * ns, sizeof(double) * (size_t)ns);
+        if (!S.grid) brute_pairs += nmodels * ns;
+        // (waits for the stream: the pinned block is packed again for the next slab)
+        if (int rc = slab_statistics(ctx, E, want, dv, q0, ns, dm, dsd, true, hquant)) return rc;
     }
-    unsigned long long cnt[4] = {0, 0, 0, 0};
-    TD_HIP(ctx, hipMemcpy(cnt, dcount, sizeof cnt, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 3; ++k) ctx->vol_counters[k] = grid && !ctx->vol_counting ? -1 : (int64_t)cnt[k];
-    ctx->vol_counters[3] = brute_pairs;
-    return TD_OK;
+    return volume_counters_finish(ctx, S, brute_pairs);
 }
 
 // the checks of both entry points that need no context and no HIP call
@@ -487,13 +446,6 @@ VolPlan volume_plan(int64_t nmodels, int64_t nq, int64_t budget, int64_t forced)
     return p;
 }
 
-void volume_free(td_ctx *ctx) {
-    if (ctx->vol) (void)hipFree(ctx->vol);
-    if (ctx->vol_grid) (void)hipFree(ctx->vol_grid);
-    ctx->vol = ctx->vol_grid = nullptr;
-    ctx->vol_cap = ctx->vol_grid_cap = 0;
-}
-
 }  // namespace tdstar
 
 using namespace tdstar;
@@ -505,43 +457,19 @@ extern "C" int td_rasterize_volume(td_ctx *ctx, int64_t nmodels, const int64_t *
     if (int rc = volume_check(ctx, vol, who)) return rc;
     if (vol->conv)
         if (int rc = conv_check_chains(ctx, nchains, chain_len, nmodels, who)) return rc;
-    const std::string w(who);
-    if (nmodels < 1 || !cell_off) return set_err(ctx, TD_ERR_ARG, w + ": need nmodels >= 1 and cell_off");
-    const int64_t total = cell_off[nmodels];
-    if (cell_off[0] != 0 || total < 0 || (total > 0 && (!xCell || !yCell || !zCell || !zeta)))
-        return set_err(ctx, TD_ERR_ARG, w + ": bad cell offsets or arrays");
-    for (int64_t k = 0; k < nmodels; ++k)
-        if (cell_off[k + 1] < cell_off[k]) return set_err(ctx, TD_ERR_ARG, w + ": offsets not monotone");
-    if (!ctx) return set_err(nullptr, TD_ERR_ARG, w + ": ctx is NULL");
-    if (vol->nq == 0) return TD_OK;
-    return volume_core(ctx, who, nmodels, cell_off, xCell, yCell, zCell, zeta, nullptr, nchains, chain_len, vol);
+    if (int rc = ensemble_check_arrays(ctx, who, nmodels, cell_off, xCell, yCell, zCell, zeta)) return rc;
+    if (!ctx) return set_err(nullptr, TD_ERR_ARG, std::string(who) + ": ctx is NULL");
+    return volume_core(ctx, who, Ensemble(nmodels, cell_off, xCell, yCell, zCell, zeta, nchains, chain_len), vol);
 }
 
 extern "C" int td_history_volume(td_ctx *ctx, td_history *const *hs, int64_t nh, const td_volume *vol) {
     const char *who = "td_history_volume";
     if (int rc = volume_check(ctx, vol, who)) return rc;
-    const std::string w(who);
-    if (!ctx) return set_err(nullptr, TD_ERR_ARG, w + ": ctx is NULL");
-    if (!hs || nh < 1) return set_err(ctx, TD_ERR_ARG, w + ": no history");
-    std::vector<td_history *> segs;
-    std::vector<int64_t> off(1, 0), lens;  // the concatenation's prefix, from the histories' host mirrors
-    for (int64_t i = 0; i < nh; ++i) {
-        td_history *h = hs[i];
-        if (!h || h->ctx != ctx) return set_err(ctx, TD_ERR_ARG, w + ": every history must be non-NULL and of this context");
-        const int64_t base = off.back();
-        for (int64_t k = 1; k <= h->samples; ++k) off.push_back(base + h->off[(size_t)k]);
-        if (h->samples > 0) {  // (one without samples is skipped)
-            segs.push_back(h);
-            lens.push_back(h->samples);
-        }
-    }
-    const int64_t nmodels = (int64_t)off.size() - 1;
-    if (nmodels < 1) return set_err(ctx, TD_ERR_ARG, w + ": the histories hold no sample");
+    Ensemble E;
+    if (int rc = ensemble_from_histories(ctx, who, hs, nh, HistoryRule::SameContext, &E)) return rc;
     if (vol->conv)
-        if (int rc = conv_check_chains(ctx, (int64_t)lens.size(), lens.data(), nmodels, who)) return rc;
-    if (vol->nq == 0) return TD_OK;
-    return volume_core(ctx, who, nmodels, off.data(), nullptr, nullptr, nullptr, nullptr, &segs, (int64_t)lens.size(),
-                       lens.data(), vol);
+        if (int rc = conv_check_chains(ctx, E.nchains, E.chain_len, E.nmodels, who)) return rc;
+    return volume_core(ctx, who, E, vol);
 }
 
 extern "C" int tdt_volume_plan(int64_t nmodels, int64_t nq, int64_t budget, int64_t forced, int64_t out[2]) {

@@ -182,6 +182,7 @@ def test_refused_calls_change_nothing(session):
     ARG = t._lib.TD_ERR_ARG
     other = co.Session()
     foreign = co.record(other, 71)
+    empty = t.History(ctx, 2, 2 * co.HISTORY["max_cells"])
     models, q = co.marg_models(), co.queries(co.MARG_NODES, 32)
     nq = len(q[0])
     bad_off = np.array([0, 8, 5], dtype=np.int64)  # not monotone, at the second model
@@ -249,6 +250,11 @@ def test_refused_calls_change_nothing(session):
         ("history_zeta_hist_1h", lambda: lib.td_history_zeta_hist(ctx.h, hs, 1, 20, 0.0, 50.0, P(hist3), None)),
         ("history_volume_1h", lambda: lib.td_history_volume(ctx.h, hs, 1, ctypes.byref(vol))),
         ("history_convergence_1h", lambda: refused(lambda: ctx.convergence_history([foreign], *q, max_lag=-1))),
+        # only histories without a sample
+        ("history_rasterize_1h", lambda: refused(lambda: ctx.rasterize_history([empty, empty], *q))),
+        ("history_volume_1h", lambda: refused(lambda: ctx.volume_history([empty], *q))),
+        ("history_predict_1h", lambda: refused(lambda: ctx.predict_history([empty]))),
+        ("history_covariance_1h", lambda: refused(lambda: ctx.covariance_history([empty, empty], *q, targets=co.COV_TARGETS))),
         ("convergence_2x40_lag0", lambda: refused(lambda: ctx.convergence(co.conv_values((40, 40)), (40, 39)))),
         ("convergence_models_4x9_lag0", lambda: refused(lambda: ctx.convergence_models(co.conv_models((9,) * 4), (9, 9, 9, 3),
                                                                                          *co.queries(co.CONV_NODES, 61)))),
@@ -268,7 +274,25 @@ def test_refused_calls_change_nothing(session):
             want = t._lib.TD_ERR_BOUNDS if name.startswith("interpolate") else ARG
             assert rc == want, (name, rc)
             co.run_checked(o, s, REFS)
+        # a history without a sample between the two of the session: skipped, the two histories' answer
+        h2 = co.session_histories(s, 2)
+        between, hq = [h2[0], empty, h2[1]], co.queries(co.H_NODES, 75)
+        routes = {
+            "rasterize": lambda: ctx.rasterize_history(between, *hq, want_values=True),
+            "volume": lambda: co.flat(ctx.volume_history(between, *hq, probs=co.MARG_PROBS, bins=(8, 0.0, 50.0),
+                                                         convergence=True, want_values=True),
+                                      ("mean", "std", "values", "quantiles", "hist", "rhat", "ess", "lags")),
+            "predict": lambda: co.flat(ctx.predict_history(between, probs=co.MARG_PROBS, convergence=True, want_values=True),
+                                       ("phi", "mean", "std", "ptS", "quantiles", "rhat", "ess", "lags")),
+            "covariance": lambda: co.flat(ctx.covariance_history(between, *hq, targets=co.COV_TARGETS),
+                                          ("cov", "corr", "mean", "std", "target_mean", "target_std")),
+        }
+        for name, route in routes.items():
+            ref = REFS.get(co.BY_NAME["history_%s_2h" % name], s.sigma_scale)
+            out = route()
+            assert co.same(out, ref), (name, co.first_difference(out, ref))
     finally:
+        empty.close()
         foreign.close()
         other.close()
 
