@@ -21,6 +21,7 @@ from .defstruct import DataStruct, Model, Ray  # noqa: F401
 from .forward import Interpolation, TdContext, context_for, evaluate, v_nearest  # noqa: F401
 from .tempering import Exchange, NativeComm, TemperingLadder, decide_swaps, geometric_ladder  # noqa: F401
 from .posterior import (convergence_maps, credible_maps, model_distributions, plot_model_hist,  # noqa: F401
-                        posterior_covariance, posterior_predictive, posterior_volume, section, trace_diagnostics)
+                        posterior_covariance, posterior_interfaces, posterior_predictive, posterior_volume, section,
+                        trace_diagnostics)
 from .sharded import RayShardedContext, ray_points, shard_rays, sub_datastruct  # noqa: F401
 from . import jld  # noqa: F401  (save/load model.jld, main_inversion.jl:18)

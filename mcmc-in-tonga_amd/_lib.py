@@ -75,7 +75,22 @@ class TdCovariance(ctypes.Structure):
                 ("std_out", _vp), ("tmean_out", _vp), ("tstd_out", _vp)]
 
 
-# name -> (restype, argtypes); every symbol declared in include/*.h
+class TdInterfaces(ctypes.Structure):
+    """td_interfaces (include/tdstar_interfaces.h); the arrays as plain addresses (ptr())."""
+    _fields_ = [("xs", _vp), ("ys", _vp), ("zs", _vp), ("nx", _i64), ("ny", _i64), ("nz", _i64), ("thr", _vp),
+                ("nthr", _i64), ("count_out", _vp), ("any_out", _vp), ("exceed_out", _vp), ("jump_out", _vp),
+                ("mean_out", _vp), ("std_out", _vp), ("density_out", _vp), ("skipped_out", _vp)]
+
+
+# name -> (restype, argtypes); every symbol declared in include/tdstar_interfaces.h, which tdstar.h does not
+# include (applied by lib() as SIGNATURES is)
+SIGNATURES_INTERFACES = {
+    "td_rasterize_interfaces": (ctypes.c_int, [_vp, _i64, _pi64, _pd, _pd, _pd, _pd, ctypes.POINTER(TdInterfaces)]),
+    "td_history_interfaces": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, ctypes.POINTER(TdInterfaces)]),
+    "tdt_interfaces_plan": (ctypes.c_int, [_i64, _i64, _i64, _i64, _i64, _i64, _pi64]),
+}
+
+# name -> (restype, argtypes); every symbol declared in include/tdstar.h and include/tdstar_testing.h
 SIGNATURES = {
     "td_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _pd, _pd, _pd, _pd, _pd, _i64, _i64, _pd, _pd]),
     "td_destroy": (ctypes.c_int, [_vp]),
@@ -225,8 +240,8 @@ def lib():
                               "(hipcc --offload-arch=gfx950); there is no CPU fallback")
         L = ctypes.CDLL(LIB_PATH)
         older = "TD_LIB_PATH" in os.environ  # (an A/B against an older build: newer testing hooks may be absent)
-        for name, (res, args) in SIGNATURES.items():
-            if older and name.startswith("tdt_") and not hasattr(L, name):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_INTERFACES.items()):
+            if older and (name.startswith("tdt_") or name in SIGNATURES_INTERFACES) and not hasattr(L, name):
                 continue
             f = getattr(L, name)
             f.restype = res

@@ -520,6 +520,79 @@ class TdContext:
 
         return self._covariance(call, nm, qx, qy, qz, targets, series, want)
 
+    IFACE_ALL = ("count", "any", "exceed", "jump", "stats", "density")
+
+    @staticmethod
+    def interfaces_plan(nmodels, nx, ny, nz, budget=0, forced=0):
+        """(the nodes a slab owns, slabs, the most columns of a slab's value matrix) of an ``interfaces`` call
+        on an nx x ny x nz lattice (budget in bytes, 0: 1 GiB); needs no GPU."""
+        out = np.zeros(3, dtype=np.int64)
+        check(lib().tdt_interfaces_plan(int(nmodels), int(nx), int(ny), int(nz), int(budget), int(forced),
+                                        ptr(out, _lib._pi64)))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def _interfaces(self, call, xs, ys, zs, thresholds, want):
+        """The td_interfaces request around ``call(byref(req))`` -> dict of the flat outputs."""
+        xs, ys, zs = (f64(np.ravel(a)) for a in (xs, ys, zs))
+        thr = f64(np.ravel(thresholds))
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not set(want) <= set(self.IFACE_ALL):
+            raise ValueError("want: a subset of %s" % (self.IFACE_ALL,))
+        nx, ny, nz, nthr = len(xs), len(ys), len(zs), len(thr)
+        nq = nx * ny * nz
+        res = dict(count=np.empty((3, nq), dtype=np.int64) if "count" in want else None,
+                   any=np.empty(nq, dtype=np.int64) if "any" in want else None,
+                   exceed=np.empty((nthr, 3, nq), dtype=np.int64) if "exceed" in want and nthr else None,
+                   jump=np.empty((3, nq)) if "jump" in want else None,
+                   mean=np.empty(nq) if "stats" in want else None, std=np.empty(nq) if "stats" in want else None,
+                   density=np.empty(nq, dtype=np.int64) if "density" in want else None, skipped=None)
+        skipped = np.zeros(1, dtype=np.int64) if "density" in want else None
+        send_thr = res["exceed"] is not None
+        i64 = _lib._pi64
+        req = _lib.TdInterfaces(ptr(xs), ptr(ys), ptr(zs), nx, ny, nz, ptr(thr) if send_thr else None,
+                                nthr if send_thr else 0, ptr(res["count"], i64), ptr(res["any"], i64),
+                                ptr(res["exceed"], i64), ptr(res["jump"]), ptr(res["mean"]), ptr(res["std"]),
+                                ptr(res["density"], i64), ptr(skipped, i64))
+        call(ctypes.byref(req))
+        if skipped is not None:
+            res["skipped"] = int(skipped[0])
+        return res
+
+    def interfaces(self, models, xs, ys, zs, thresholds=(), want=IFACE_ALL):
+        """td_rasterize_interfaces: where the models put their Voronoi boundaries on the lattice ``xs`` x ``ys``
+        x ``zs`` (node n = i + nx (j + ny k), x fastest), how large the jump across them is, and where the cells
+        lie.  With d = V[m][n + s_a] - V[m][n] on the forward face of node n along axis a (x, y, z) -> dict of
+        flat arrays: count[3, nq] the models whose value differs across the face, any[nq] the models that differ
+        across at least one of the node's faces, exceed[nthr, 3, nq] the models with abs(d) > thresholds[t], jump[3,
+        nq] the mean of abs(d) over the models in ``rasterize``'s association (-1 / NaN where there is no face),
+        mean[nq], std[nq] (``volume``'s), density[nq] the cells of all models whose nucleus lies in the node's voxel
+        (bounded by the midpoints between nodes, the edge voxels open outwards) and skipped, the cells with a NaN
+        coordinate.  ``want``: the subset of IFACE_ALL to compute ("stats": mean and std); what is not asked
+        for, and exceed without thresholds, is None.  Any number of nodes, swept slab by slab as by ``volume``
+        with the halo of the forward neighbours.  models as for ``rasterize``."""
+        off = np.zeros(len(models) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(m[0]) for m in models])
+        cat = [f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) if len(models) else np.zeros(0)
+               for k in range(4)]
+
+        def call(req):
+            check(lib().td_rasterize_interfaces(self.h, len(models), ptr(off, _lib._pi64), *(ptr(c) for c in cat), req),
+                  self.h)
+
+        return self._interfaces(call, xs, ys, zs, thresholds, want)
+
+    def interfaces_history(self, histories, xs, ys, zs, thresholds=(), want=IFACE_ALL):
+        """td_history_interfaces: ``interfaces`` on the samples of the histories (chain.History) where they lie,
+        history by history (one without samples is skipped); they may have been recorded on another context of
+        this device."""
+        histories = list(histories)
+        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
+
+        def call(req):
+            check(lib().td_history_interfaces(self.h, hs, len(histories), req), self.h)
+
+        return self._interfaces(call, xs, ys, zs, thresholds, want)
+
     def interpolate(self, cells, X, Y, Z, want_nearest=False):
         """-> (zeta[npoints], nearest[npoints] or None)"""
         xc, yc, zc, ze = (f64(c) for c in cells)

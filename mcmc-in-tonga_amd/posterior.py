@@ -260,6 +260,48 @@ def posterior_covariance(model_hist, dataStruct, TD_parameters, targets, series=
     return out
 
 
+def posterior_interfaces(model_hist, dataStruct, TD_parameters, thresholds=(5.0,), xs=None, ys=None, zs=None):
+    """Where the ensemble puts boundaries: what the other posterior products smooth over.  On the lattice
+    ``xs`` x ``ys`` x ``zs`` (default: dataStruct.xVec / yVec / zVec), with d the difference of a model's
+    nearest-cell zeta across the forward face of a node along axis a (0: x, 1: y, 2: z), -> dict of [nx, ny, nz]
+    arrays: ``prob`` [3, ...] the share of the models with a Voronoi boundary on the face (the value differs),
+    ``prob_any`` the share with one on any of the node's forward faces, ``exceed`` [nthr, 3, ...] the share with
+    abs(d) > thresholds[t], ``jump`` [3, ...] the expected abs(d) (NaN where the lattice ends and there is no
+    face), ``count`` [3, ...] and ``any`` the raw counts (-1 without a face), ``density`` the cells of all models
+    whose nucleus lies in the node's voxel, ``density_per_model`` (= density / M: where the sampler spends its
+    cells), ``skipped`` (cells with a NaN coordinate), ``mean``, ``std`` (``posterior_volume``'s) and ``x``,
+    ``y``, ``z``, ``thresholds``.  Same inputs as ``posterior_volume`` (Models, nested lists, a ``History`` or a
+    list of them); computed on the device slab by slab (td_rasterize_interfaces / td_history_interfaces)."""
+    ctx = context_for(dataStruct)  # (TD_parameters: the siblings' signature; the lattice decides everything here)
+    xv, yv, zv = (np.asarray(v if v is not None else d, dtype=np.float64).ravel()
+                  for v, d in ((xs, dataStruct.xVec), (ys, dataStruct.yVec), (zs, dataStruct.zVec)))
+    thr = np.asarray(thresholds, dtype=np.float64).ravel()
+    shape = (len(zv), len(yv), len(xv))  # x fastest
+    models, lens = _chains(model_hist)
+    if _on_device(models):
+        r = ctx.interfaces_history(models, xv, yv, zv, thr)
+    else:
+        r = ctx.interfaces([m.cells() for m in models], xv, yv, zv, thr)
+    M = sum(lens)
+
+    def grid(a):  # [..., nq] -> [..., nx, ny, nz]
+        lead = a.shape[:-1]
+        k = len(lead)
+        return a.reshape(lead + shape).transpose(tuple(range(k)) + (k + 2, k + 1, k)).copy()
+
+    def share(c):
+        return np.where(c < 0, np.nan, c / np.float64(M))
+
+    out = {"x": xv, "y": yv, "z": zv, "thresholds": thr, "skipped": r["skipped"]}
+    for f in ("count", "any", "jump", "mean", "std", "density"):
+        out[f] = grid(r[f])
+    out["prob"] = share(out["count"])
+    out["prob_any"] = share(out["any"])
+    out["exceed"] = share(grid(r["exceed"])) if r["exceed"] is not None else np.empty((0, 3) + shape[::-1])
+    out["density_per_model"] = out["density"] / np.float64(M)
+    return out
+
+
 def posterior_predictive(model_hist, dataStruct, TD_parameters, probs=(0.05, 0.5, 0.95), bins=None, convergence=False,
                          values=False, max_lag=0):
     """Does the ensemble fit the data, ray by ray, and does it predict data it was not fitted to?  Every
