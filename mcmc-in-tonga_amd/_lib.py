@@ -90,6 +90,23 @@ SIGNATURES_INTERFACES = {
     "tdt_interfaces_plan": (ctypes.c_int, [_i64, _i64, _i64, _i64, _i64, _i64, _pi64]),
 }
 
+
+class TdRegions(ctypes.Structure):
+    """td_regions (include/tdstar_regions.h); the arrays and the two optional requests as plain addresses (ptr(),
+    ctypes.addressof)."""
+    _fields_ = [("px", _vp), ("py", _vp), ("pz", _vp), ("w", _vp), ("np", _i64), ("reg_off", _vp), ("nreg", _i64),
+                ("normalize", _i64), ("series_out", _vp), ("weight_out", _vp), ("mean_out", _vp), ("std_out", _vp),
+                ("greater_out", _vp), ("marg", _vp), ("conv", _vp)]
+
+
+# name -> (restype, argtypes); every symbol declared in include/tdstar_regions.h, which tdstar.h does not include
+# (applied by lib() as SIGNATURES is)
+SIGNATURES_REGIONS = {
+    "td_rasterize_regions": (ctypes.c_int, [_vp, _i64, _pi64, _pd, _pd, _pd, _pd, _i64, _pi64, ctypes.POINTER(TdRegions)]),
+    "td_history_regions": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, ctypes.POINTER(TdRegions)]),
+    "tdt_regions_plan": (ctypes.c_int, [_i64, _i64, _i64, _i64, _pi64]),
+}
+
 # name -> (restype, argtypes); every symbol declared in include/tdstar.h and include/tdstar_testing.h
 SIGNATURES = {
     "td_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _pd, _pd, _pd, _pd, _pd, _i64, _i64, _pd, _pd]),
@@ -240,8 +257,9 @@ def lib():
                               "(hipcc --offload-arch=gfx950); there is no CPU fallback")
         L = ctypes.CDLL(LIB_PATH)
         older = "TD_LIB_PATH" in os.environ  # (an A/B against an older build: newer testing hooks may be absent)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_INTERFACES.items()):
-            if older and (name.startswith("tdt_") or name in SIGNATURES_INTERFACES) and not hasattr(L, name):
+        later = dict(SIGNATURES_INTERFACES, **SIGNATURES_REGIONS)  # (the headers of their own)
+        for name, (res, args) in list(SIGNATURES.items()) + list(later.items()):
+            if older and (name.startswith("tdt_") or name in later) and not hasattr(L, name):
                 continue
             f = getattr(L, name)
             f.restype = res

@@ -1,0 +1,369 @@
+// regions.hip -- posterior region averages: per model the weighted sum (or average) of the nearest-cell value
+// over each region of a point list, and on that matrix F[M][regions] the statistics of a posterior volume with
+// the regions in the place of the nodes (include/tdstar_regions.h holds the contract).
+//
+// The search structure is the volume's (volume_build).  The point list is swept slab by slab of volume_plan's
+// columns; a slab's V_slab[M][ns] (volume_sweep) is reduced over its COLUMNS, per model, in td_rasterize's
+// association counted over the index within the region.  The unit of that association is the leaf: a block of
+// at most 1024 consecutive points of one region (region_leaves: the split of iface_leaves applied to the
+// region's point count).  The leaves of all regions tile the point list in order.
+//   k_region_sums     work item = (a leaf's columns in this slab, 64 models), one wave, one lane per model.
+//                     V_slab is row-major, so a lane walking its own row would stride by 8 ns bytes: the wave
+//                     reads a tile of 64 models x 64 columns row by row instead -- each row one coalesced
+//                     512-byte load, kRegAhead of them in flight per lane -- into LDS (rows padded to 65
+//                     doubles: lane m's ds_read_b64 of column c hits the bank pair 2 (m + c) mod 64, none twice
+//                     in a half wave), with the tile's weights as one more LDS row; then each lane walks its row
+//                     left to right, t = w * v rounded, then acc = acc + t.  A leaf is summed left to right, so
+//                     a slab boundary inside it is carried: the accumulators acc[leaf][M] live in the workspace
+//                     across the slabs, started at -0.0 (-0.0 + t is t for every t, the sign of a zero
+//                     included) where the leaf begins.
+//   k_region_combine  one lane per (model, region): the region's leaf sums are added in the tree's order (the
+//                     walk of k_iface_combine with a leaf as the unit, the waiting left halves in LDS), divided
+//                     by W[r] when asked, and written to F[m][r].  W is formed on the host in the same
+//                     association.
+//   k_region_greater  greater[a][b] over the rows of F: a workgroup takes 16 x 16 pairs and a chunk of models
+//                     through LDS, one lane per pair, and adds its 32-bit count with one 64-bit atomic (integer
+//                     sums: any order gives the same number).
+// The tail is slab_statistics on (F, M, regions): k_raster_stats, marginals_run and convergence_run as a volume
+// runs them.
+#pragma clang fp contract(off)
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/tdstar_regions.h"
+#include "covariance.h"
+#include "ctx.h"
+#include "ensemble.h"
+#include "history.h"
+#include "volume.h"
+
+namespace tdstar {
+
+namespace {
+
+constexpr int kRegTile = 64;          // models and columns of an LDS tile; one wave
+constexpr int kRegPad = kRegTile + 1; // doubles per LDS row
+constexpr int kRegAhead = 16;         // rows of the tile a lane keeps in flight
+constexpr int kRegPairs = 16;         // k_region_greater: 16 x 16 pairs per workgroup
+constexpr int kRegChunk = 1024;       // ... and this many models, 64 at a time through LDS
+constexpr int64_t kRegMaxRegions = kVolMaxSlabNodes;             // the statistics take one slab's columns
+constexpr int64_t kRegMaxCounters = kVolDefaultBudget / 8;       // greater_out: 1 GiB of 64-bit counters
+
+// V = V_slab[M][ns], the points [c0, c0 + ns) of the list.  Leaf l is the points [leafp[l], leafp[l + 1]);
+// workgroup b takes the leaf la + b / mgroups and the models 64 (b % mgroups) ...  wcol [ns]: the slab's weights
+// (null: 1.0).  acc [leaves][M].
+__global__ __launch_bounds__(kRegTile) void k_region_sums(const double *__restrict__ V, long ns, int M, long c0,
+                                                          const long long *__restrict__ leafp, long la, int mgroups,
+                                                          const double *__restrict__ wcol, double *__restrict__ acc) {
+    __shared__ double tile[kRegTile * kRegPad];
+    __shared__ double wrow[kRegTile];
+    const int lane = threadIdx.x;
+    const long leaf = la + blockIdx.x / mgroups;
+    const int m0 = (int)(blockIdx.x % mgroups) * kRegTile;
+    const long p0 = leafp[leaf], p1 = leafp[leaf + 1];
+    const long s0 = max(p0, c0) - c0, s1 = min(p1, c0 + ns) - c0;  // the leaf's columns of this slab: [s0, s1)
+    const int m = min(m0 + lane, M - 1);
+    double a = p0 >= c0 ? -0.0 : acc[leaf * M + m];  // the leaf begins here, or is carried from the slab before
+    const double *__restrict__ mine = tile + lane * kRegPad;
+    for (long t0 = s0; t0 < s1; t0 += kRegTile) {
+        const int nc = (int)min((long)kRegTile, s1 - t0);
+        const long col = t0 + min(lane, nc - 1);  // (past the leaf's end: its last column again, not used)
+        wrow[lane] = wcol ? wcol[col] : 1.0;
+#pragma unroll
+        for (int j0 = 0; j0 < kRegTile; j0 += kRegAhead) {
+            double r[kRegAhead];
+#pragma unroll
+            for (int j = 0; j < kRegAhead; ++j) r[j] = V[(long)min(m0 + j0 + j, M - 1) * ns + col];
+#pragma unroll
+            for (int j = 0; j < kRegAhead; ++j) tile[(j0 + j) * kRegPad + lane] = r[j];
+        }
+        __syncthreads();
+        if (nc == kRegTile) {
+#pragma unroll 16
+            for (int c = 0; c < kRegTile; ++c) {
+                const double t = wrow[c] * mine[c];
+                a = a + t;
+            }
+        } else {
+            for (int c = 0; c < nc; ++c) {
+                const double t = wrow[c] * mine[c];
+                a = a + t;
+            }
+        }
+        __syncthreads();  // (the tile is filled again)
+    }
+    if (m0 + lane < M) acc[leaf * M + m0 + lane] = a;
+}
+
+// Region r's leaves are regleaf[r] .. regleaf[r + 1] - 1.  Workgroup b: region b / mblocks, models 256 (b % mblocks) ...
+__global__ __launch_bounds__(256) void k_region_combine(const double *__restrict__ acc, int M, int mblocks,
+                                                        const long long *__restrict__ regleaf,
+                                                        const long long *__restrict__ leafp,
+                                                        const double *__restrict__ W, int normalize, long R,
+                                                        double *__restrict__ F) {
+    extern __shared__ double pend[];  // the waiting left halves [cov_levels(the most points of a region)][256]
+    const long r = blockIdx.x / mblocks;
+    const int m = (int)(blockIdx.x % mblocks) * 256 + threadIdx.x;
+    if (m >= M) return;
+    const long l0 = regleaf[r], nl = regleaf[r + 1] - l0;
+    const long n = leafp[l0 + nl] - leafp[l0];  // the region's points
+    const double *__restrict__ ps = acc + l0 * M + m;
+    double total;
+    if (nl == 1) {
+        total = ps[0];
+    } else {  // k_iface_combine's walk of the pairwise tree over the region's n points, a block of <= 1024 being a leaf
+        unsigned path = 0;  // bit d: the right child at depth d
+        int depth = 0, nv = 0;
+        long leaf = 0;
+        for (;;) {
+            long lo = 0, hi = n - 1;
+            for (int d = 0; d < depth; ++d) {
+                const long mid = lo + ((hi - lo) >> 1);
+                if ((path >> d) & 1u)
+                    lo = mid + 1;
+                else
+                    hi = mid;
+            }
+            while (hi - lo >= 1024) {  // down the left children to a block
+                hi = lo + ((hi - lo) >> 1);
+                path &= ~(1u << depth);
+                ++depth;
+            }
+            total = ps[leaf * M];
+            ++leaf;
+            while (depth > 0 && ((path >> (depth - 1)) & 1u)) {  // a right child: its parent is left + right
+                --nv;
+                total = pend[nv * 256 + threadIdx.x] + total;
+                --depth;
+            }
+            if (depth == 0) break;
+            pend[nv * 256 + threadIdx.x] = total;  // a left child waits (read again by this lane alone)
+            ++nv;
+            path |= 1u << (depth - 1);
+        }
+    }
+    F[(long)m * R + r] = normalize ? total / W[r] : total;
+}
+
+// cnt [R][R], zeroed.  Workgroup (x: chunk of kRegChunk models, y: 16 regions b, z: 16 regions a).
+__global__ __launch_bounds__(256) void k_region_greater(const double *__restrict__ F, int M, long R,
+                                                        unsigned long long *__restrict__ cnt) {
+    __shared__ double sa[64 * (kRegPairs + 1)], sb[64 * (kRegPairs + 1)];
+    const int t = threadIdx.x, i = t / kRegPairs, j = t % kRegPairs;
+    const long ra = (long)blockIdx.z * kRegPairs, rb = (long)blockIdx.y * kRegPairs;
+    const long mbeg = (long)blockIdx.x * kRegChunk, mend = min(mbeg + kRegChunk, (long)M);
+    unsigned count = 0;
+    for (long mm = mbeg; mm < mend; mm += 64) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {  // 64 rows x 16 columns of each side; what lies outside is NaN (> is false)
+            const int e = t + 256 * k, row = e / kRegPairs, c = e % kRegPairs;
+            const bool in = mm + row < mend;
+            sa[row * (kRegPairs + 1) + c] = in && ra + c < R ? F[(mm + row) * R + ra + c] : __builtin_nan("");
+            sb[row * (kRegPairs + 1) + c] = in && rb + c < R ? F[(mm + row) * R + rb + c] : __builtin_nan("");
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int row = 0; row < 64; ++row) count += sa[row * (kRegPairs + 1) + i] > sb[row * (kRegPairs + 1) + j];
+        __syncthreads();
+    }
+    if (count > 0 && ra + i < R && rb + j < R) atomicAdd(&cnt[(ra + i) * R + rb + j], (unsigned long long)count);
+}
+
+// The leaves of a region of n points whose first point is `base`, in order: the first points, appended to out.
+void region_leaves(int64_t base, int64_t lo, int64_t hi, std::vector<long long> *out) {
+    if (hi - lo < 1024) {
+        out->push_back(base + lo);
+        return;
+    }
+    const int64_t mid = (lo + hi) >> 1;
+    region_leaves(base, lo, mid, out);
+    region_leaves(base, mid + 1, hi, out);
+}
+
+// W of one region: the sum of w[lo .. hi] (null: of ones) in the tree's order, a block left to right.
+double region_weight(const double *w, int64_t lo, int64_t hi) {
+    if (hi - lo < 1024) {
+        double s = w ? w[lo] : 1.0;
+        for (int64_t k = lo + 1; k <= hi; ++k) s = s + (w ? w[k] : 1.0);
+        return s;
+    }
+    const int64_t mid = (lo + hi) >> 1;
+    const double a = region_weight(w, lo, mid), b = region_weight(w, mid + 1, hi);
+    return a + b;
+}
+
+// the checks of both entry points that need no context and no HIP call, in the header's order
+int regions_check(td_ctx *ctx, const td_regions *w, const char *who) {
+    const std::string n(who);
+    if (!w) return set_err(ctx, TD_ERR_ARG, n + ": want is NULL");
+    if (w->np < 1 || w->nreg < 1) return set_err(ctx, TD_ERR_ARG, n + ": np and nreg must be >= 1");
+    if (!w->px || !w->py || !w->pz || !w->reg_off) return set_err(ctx, TD_ERR_ARG, n + ": px, py, pz and reg_off must be given");
+    if (w->reg_off[0] != 0) return set_err(ctx, TD_ERR_ARG, n + ": reg_off[0] must be 0");
+    for (int64_t r = 0; r < w->nreg; ++r) {
+        if (w->reg_off[r + 1] < w->reg_off[r]) return set_err(ctx, TD_ERR_ARG, n + ": reg_off is not monotone");
+        if (w->reg_off[r + 1] == w->reg_off[r]) return set_err(ctx, TD_ERR_ARG, n + ": a region without points");
+        if (w->reg_off[r + 1] > w->np) return set_err(ctx, TD_ERR_ARG, n + ": reg_off[nreg] must be np");
+    }
+    if (w->reg_off[w->nreg] != w->np) return set_err(ctx, TD_ERR_ARG, n + ": reg_off[nreg] must be np");
+    const double *vec[4] = {w->px, w->py, w->pz, w->w};
+    const char *name[4] = {"px", "py", "pz", "w"};
+    for (int a = 0; a < 4; ++a)
+        for (int64_t i = 0; vec[a] && i < w->np; ++i)
+            if (!std::isfinite(vec[a][i])) return set_err(ctx, TD_ERR_ARG, n + ": " + name[a] + " is not finite");
+    if (w->normalize != 0 && w->normalize != 1) return set_err(ctx, TD_ERR_ARG, n + ": normalize must be 0 or 1");
+    if (!w->series_out && !w->weight_out && !w->mean_out && !w->std_out && !w->greater_out && !w->marg && !w->conv)
+        return set_err(ctx, TD_ERR_ARG, n + ": no output asked for");
+    if (!w->mean_out != !w->std_out) return set_err(ctx, TD_ERR_ARG, n + ": mean_out and std_out must be given together");
+    if (w->marg)
+        if (int rc = marg_check_want(ctx, w->marg, who)) return rc;
+    if (w->conv)
+        if (int rc = conv_check_want(ctx, w->conv, who)) return rc;
+    return TD_OK;
+}
+
+// Both entry points; E and w have been checked (ensemble.h, regions_check).
+int regions_core(td_ctx *ctx, const char *who, const Ensemble &E, const td_regions *w) {
+    const std::string n(who);
+    const int64_t M = E.nmodels, np = w->np, R = w->nreg;
+    if (R > kRegMaxRegions) return set_err(ctx, TD_ERR_ARG, n + ": more than 2^18 regions");
+    if (M > kVolDefaultBudget / 8 / R)
+        return set_err(ctx, TD_ERR_ARG, n + ": the series [nmodels][nreg] exceed 1 GiB");
+    if (w->greater_out && R * R > kRegMaxCounters)
+        return set_err(ctx, TD_ERR_ARG, n + ": greater_out of more than 2^27 counters (1 GiB)");
+    // the leaves of all regions behind one another: leaf l = the points [leafp[l], leafp[l + 1])
+    std::vector<long long> leafp, regleaf((size_t)R + 1);
+    std::vector<double> W((size_t)R);
+    int64_t most = 1;
+    for (int64_t r = 0; r < R; ++r) {
+        const int64_t lo = w->reg_off[r], cnt = w->reg_off[r + 1] - lo;
+        regleaf[(size_t)r] = (long long)leafp.size();
+        region_leaves(lo, 0, cnt - 1, &leafp);
+        W[(size_t)r] = region_weight(w->w ? w->w + lo : nullptr, 0, cnt - 1);
+        most = std::max(most, cnt);
+    }
+    const int64_t L = (int64_t)leafp.size();
+    regleaf[(size_t)R] = L;
+    leafp.push_back(np);
+    if (M > kVolDefaultBudget / 8 / L)
+        return set_err(ctx, TD_ERR_ARG, n + ": the leaf sums [leaves][nmodels] exceed 1 GiB");
+    if (int rc = marg_check_models(ctx, w->marg, M)) return rc;  // (before anything is issued)
+    const VolPlan plan = volume_plan(M, np, kVolDefaultBudget, ctx->vol_slab_nodes);
+    const int64_t cap = std::min(plan.nodes, np);
+    const int mgroups = (int)((M + kRegTile - 1) / kRegTile), mblocks = (int)((M + 255) / 256);
+    if ((cap + 1) * (int64_t)mgroups > INT32_MAX || R * (int64_t)mblocks > INT32_MAX)
+        return set_err(ctx, TD_ERR_ARG, n + ": too many models for one launch");
+    TD_HIP(ctx, hipSetDevice(ctx->device));
+    servers_quiesce(nullptr);
+    VolSearch S;
+    if (int rc = volume_build(ctx, who, E, &S)) return rc;
+    hipStream_t s = ctx->stream;
+    Timer *tm = ctx->timer.on ? &ctx->timer : nullptr;
+    // ctx->raster (8-byte words): queries [3][cap] | weights [cap] | V_slab [M][cap] | mean, std [R] | leaf sums
+    // [L][M] | F [M][R] | W [R] | counters [R][R] | leafp [L + 1] | regleaf [R + 1]; pinned: queries | weights
+    const size_t n_q = 3 * (size_t)cap, n_w = (size_t)cap, n_v = (size_t)M * (size_t)cap, n_ms = 2 * (size_t)R,
+                 n_acc = (size_t)L * (size_t)M, n_F = (size_t)M * (size_t)R, n_W = (size_t)R,
+                 n_cnt = w->greater_out ? (size_t)R * (size_t)R : 0, n_lp = (size_t)L + 1, n_rl = (size_t)R + 1;
+    if (int rc = raster_reserve(ctx, n_q + n_w + n_v + n_ms + n_acc + n_F + n_W + n_cnt + n_lp + n_rl, n_q + n_w)) return rc;
+    double *dq = ctx->raster.as<double>(), *dw = dq + n_q, *dv = dw + n_w, *dm = dv + n_v, *dsd = dm + R, *dacc = dsd + R,
+           *dF = dacc + n_acc, *dW = dF + n_F;
+    unsigned long long *dcnt = reinterpret_cast<unsigned long long *>(dW + n_W);
+    long long *dlp = reinterpret_cast<long long *>(dW + n_W + n_cnt), *drl = dlp + n_lp;
+    double *hw = ctx->h_raster.as<double>() + n_q;
+    TD_HIP(ctx, hipStreamSynchronize(s));  // (the pinned block and the workspace are free)
+    TD_HIP(ctx, hipMemcpyAsync(dlp, leafp.data(), sizeof(long long) * n_lp, hipMemcpyHostToDevice, s));
+    TD_HIP(ctx, hipMemcpyAsync(drl, regleaf.data(), sizeof(long long) * n_rl, hipMemcpyHostToDevice, s));
+    TD_HIP(ctx, hipMemcpyAsync(dW, W.data(), sizeof(double) * n_W, hipMemcpyHostToDevice, s));
+    int64_t brute_pairs = 0, la = 0;  // la: the first leaf with a point in the slab
+    for (int64_t c0 = 0; c0 < np; c0 += plan.nodes) {
+        const int64_t ns = std::min(plan.nodes, np - c0);
+        if (int rc = stage_queries(ctx, w->px, w->py, w->pz, c0, ns, dq)) return rc;
+        if (w->w) {
+            std::memcpy(hw, w->w + c0, sizeof(double) * (size_t)ns);
+            TD_HIP(ctx, hipMemcpyAsync(dw, hw, sizeof(double) * (size_t)ns, hipMemcpyHostToDevice, s));
+        }
+        if (int rc = volume_sweep(ctx, S, 0, M, dq, ns, dv)) return rc;
+        if (!S.grid) brute_pairs += M * ns;
+        while (leafp[(size_t)la + 1] <= c0) ++la;
+        int64_t lb = la;  // the last leaf with a point in the slab
+        while (leafp[(size_t)lb + 1] < c0 + ns) ++lb;
+        hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
+        hipLaunchKernelGGL(k_region_sums, dim3((unsigned)((lb - la + 1) * mgroups)), dim3(kRegTile), 0, s, dv, (long)ns, (int)M,
+                           (long)c0, dlp, (long)la, mgroups, w->w ? dw : nullptr, dacc);
+        if (tm) tm->end("region_sums", t0, s);
+        TD_HIP(ctx, hipGetLastError());
+        TD_HIP(ctx, hipStreamSynchronize(s));  // the pinned block is packed again for the next slab
+    }
+    {
+        hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
+        hipLaunchKernelGGL(k_region_combine, dim3((unsigned)(R * mblocks)), dim3(256), sizeof(double) * 256 * (size_t)cov_levels(most),
+                           s, dacc, (int)M, mblocks, drl, dlp, dW, (int)w->normalize, (long)R, dF);
+        if (tm) tm->end("region_combine", t0, s);
+        TD_HIP(ctx, hipGetLastError());
+    }
+    if (w->greater_out) {
+        TD_HIP(ctx, hipMemsetAsync(dcnt, 0, sizeof(unsigned long long) * n_cnt, s));
+        const unsigned tiles = (unsigned)((R + kRegPairs - 1) / kRegPairs);
+        hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
+        hipLaunchKernelGGL(k_region_greater, dim3((unsigned)((M + kRegChunk - 1) / kRegChunk), tiles, tiles), dim3(256), 0, s, dF,
+                           (int)M, (long)R, dcnt);
+        if (tm) tm->end("region_greater", t0, s);
+        TD_HIP(ctx, hipGetLastError());
+        TD_HIP(ctx, hipMemcpyAsync(w->greater_out, dcnt, sizeof(int64_t) * n_cnt, hipMemcpyDeviceToHost, s));
+    }
+    {  // the regions in the place of a slab's columns: the slab is the whole matrix
+        const SlabWant want{R, w->mean_out, w->std_out, w->series_out, w->marg, w->conv};
+        hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
+        const int rc = slab_statistics(ctx, E, want, dF, 0, R, dm, dsd, false, nullptr);
+        if (tm) tm->end("raster_stats", t0, s);
+        if (rc) return rc;
+    }
+    TD_HIP(ctx, hipStreamSynchronize(s));
+    if (w->weight_out) std::memcpy(w->weight_out, W.data(), sizeof(double) * n_W);
+    return volume_counters_finish(ctx, S, brute_pairs);  // (tdt_volume_counters: this call's sweeps)
+}
+
+}  // namespace
+
+}  // namespace tdstar
+
+using namespace tdstar;
+
+extern "C" int td_rasterize_regions(td_ctx *ctx, int64_t nmodels, const int64_t *cell_off, const double *xCell,
+                                    const double *yCell, const double *zCell, const double *zeta, int64_t nchains,
+                                    const int64_t *chain_len, const td_regions *want) {
+    const char *who = "td_rasterize_regions";
+    if (int rc = regions_check(ctx, want, who)) return rc;
+    if (want->conv)
+        if (int rc = conv_check_chains(ctx, nchains, chain_len, nmodels, who)) return rc;
+    if (int rc = ensemble_check_arrays(ctx, who, nmodels, cell_off, xCell, yCell, zCell, zeta)) return rc;
+    if (!ctx) return set_err(nullptr, TD_ERR_ARG, std::string(who) + ": ctx is NULL");
+    return regions_core(ctx, who, Ensemble(nmodels, cell_off, xCell, yCell, zCell, zeta, nchains, chain_len), want);
+}
+
+extern "C" int td_history_regions(td_ctx *ctx, td_history *const *hs, int64_t nh, const td_regions *want) {
+    const char *who = "td_history_regions";
+    if (int rc = regions_check(ctx, want, who)) return rc;
+    Ensemble E;
+    if (int rc = ensemble_from_histories(ctx, who, hs, nh, HistoryRule::SameDevice, &E)) return rc;
+    if (want->conv)  // (one history with samples is one chain)
+        if (int rc = conv_check_chains(ctx, E.nchains, E.chain_len, E.nmodels, who)) return rc;
+    if (int rc = ensemble_check_device(ctx, who, E)) return rc;  // (of the first history's device without a context)
+    if (!ctx) return set_err(nullptr, TD_ERR_ARG, std::string(who) + ": ctx is NULL");
+    if (int rc = ensemble_sync_foreign(ctx, E)) return rc;
+    return regions_core(ctx, who, E, want);
+}
+
+extern "C" int tdt_regions_plan(int64_t nmodels, int64_t np, int64_t budget, int64_t forced, int64_t out[2]) {
+    if (!out || nmodels < 1 || np < 1 || budget < 0 || forced < 0) return TD_ERR_ARG;
+    const VolPlan p = volume_plan(nmodels, np, budget, forced);
+    out[0] = p.nodes;
+    out[1] = p.nslabs;
+    return TD_OK;
+}

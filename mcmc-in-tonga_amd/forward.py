@@ -593,6 +593,83 @@ class TdContext:
 
         return self._interfaces(call, xs, ys, zs, thresholds, want)
 
+    @staticmethod
+    def regions_plan(nmodels, npoints, budget=0, forced=0):
+        """(the points a slab sweeps, slabs) of a ``regions`` call on ``npoints`` points (budget in bytes, 0:
+        1 GiB): ``volume_plan``'s numbers with the point list in the place of the nodes; needs no GPU."""
+        out = np.zeros(2, dtype=np.int64)
+        check(lib().tdt_regions_plan(int(nmodels), int(npoints), int(budget), int(forced), ptr(out, _lib._pi64)))
+        return int(out[0]), int(out[1])
+
+    def _regions(self, call, nmodels, px, py, pz, reg_off, w, normalize, probs, bins, conv, max_lag, greater):
+        """The td_regions request around ``call(byref(req))`` -> dict of the outputs."""
+        px, py, pz = (f64(np.ravel(a)) for a in (px, py, pz))
+        npts = len(px)
+        if not (len(py) == len(pz) == npts):
+            raise ValueError("px, py and pz must have the same length")
+        wv = f64(np.ravel(w)) if w is not None else None
+        if wv is not None and len(wv) != npts:
+            raise ValueError("w must have one weight per point")
+        off = np.ascontiguousarray(reg_off, dtype=np.int64).ravel()
+        R = len(off) - 1
+        if R < 1:
+            raise ValueError("reg_off must hold nreg + 1 >= 2 offsets")
+        res = dict(series=np.empty((nmodels, R)), weight=np.empty(R), mean=np.empty(R), std=np.empty(R),
+                   greater=np.empty((R, R), dtype=np.int64) if greater else None, quantiles=None, hist=None)
+        held = []
+        marg = cw = None
+        if len(np.ravel(probs)) or bins is not None:
+            marg, arrays, res["quantiles"], res["hist"] = self._marginals_want(R, probs, bins)
+            held.append(arrays)
+        if conv:
+            cw, arrays = self._convergence_want(R, max_lag, self.CONV_ALL)
+            res.update(arrays)
+        req = _lib.TdRegions(ptr(px), ptr(py), ptr(pz), ptr(wv), npts, ptr(off, _lib._pi64), R, int(bool(normalize)),
+                             ptr(res["series"]), ptr(res["weight"]), ptr(res["mean"]), ptr(res["std"]),
+                             ptr(res["greater"], _lib._pi64), ctypes.addressof(marg) if marg is not None else None,
+                             ctypes.addressof(cw) if cw is not None else None)
+        call(ctypes.byref(req))
+        del held
+        return res
+
+    def regions(self, models, px, py, pz, reg_off, w=None, normalize=True, probs=(), bins=None, chain_len=None,
+                max_lag=0, greater=True):
+        """td_rasterize_regions: one number per model and region.  Region r is the points ``reg_off[r] ..
+        reg_off[r + 1] - 1`` of ``px``, ``py``, ``pz`` with the weights ``w`` (None: 1.0; a point may be listed in
+        several regions, a weight may be negative).  With V[m][p] the nearest-cell value of model m at point p
+        (``volume``'s) -> dict(series[nmodels, R] = the sum over the region of w[p] * V[m][p] in ``rasterize``'s
+        association over the index within the region, divided by weight[R] (the sum of w in the same association)
+        when ``normalize``; mean[R], std[R] over the models; greater[R, R] = the models with series[m, a] >
+        series[m, b] (None unless ``greater``); quantiles[nprob, R] or None; hist[R, nbins + 3] or None; with ``chain_len`` (the rows of
+        each chain) rhat, ess, lags [R]) -- the statistics are ``volume``'s with the regions in the place of the
+        nodes.  Any number of points, swept slab by slab as by ``volume``.  models as for ``rasterize``."""
+        off = np.zeros(len(models) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(m[0]) for m in models])
+        cat = [f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) if len(models) else np.zeros(0)
+               for k in range(4)]
+        lens = np.ascontiguousarray(chain_len, dtype=np.int64).ravel() if chain_len is not None else None
+
+        def call(req):
+            check(lib().td_rasterize_regions(self.h, len(models), ptr(off, _lib._pi64), *(ptr(c) for c in cat),
+                                             len(lens) if lens is not None else 0, ptr(lens, _lib._pi64), req), self.h)
+
+        return self._regions(call, len(models), px, py, pz, reg_off, w, normalize, probs, bins, lens is not None, max_lag,
+                             greater)
+
+    def regions_history(self, histories, px, py, pz, reg_off, w=None, normalize=True, probs=(), bins=None,
+                        convergence=False, max_lag=0, greater=True):
+        """td_history_regions: ``regions`` on the samples of the histories (chain.History) where they lie, history
+        by history (one without samples is skipped); they may have been recorded on another context of this
+        device.  With ``convergence`` one history is one chain."""
+        histories = list(histories)
+        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
+        nm = sum(len(h) for h in histories)
+
+        def call(req):
+            check(lib().td_history_regions(self.h, hs, len(histories), req), self.h)
+
+        return self._regions(call, nm, px, py, pz, reg_off, w, normalize, probs, bins, convergence, max_lag, greater)
+
     def interpolate(self, cells, X, Y, Z, want_nearest=False):
         """-> (zeta[npoints], nearest[npoints] or None)"""
         xc, yc, zc, ze = (f64(c) for c in cells)

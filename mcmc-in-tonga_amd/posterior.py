@@ -302,6 +302,111 @@ def posterior_interfaces(model_hist, dataStruct, TD_parameters, thresholds=(5.0,
     return out
 
 
+def voxel_weights(xs, ys, zs):
+    """The volume of every node's voxel, [nx, ny, nz]: (dx_i * dy_j) * dz_k.  Along an axis of n >= 2 nodes v the
+    widths are the differences of the edges [v_0, the midpoints 0.5 (v_l + v_{l+1}) ..., v_{n-1}] (the end nodes
+    own half a cell); an axis of one node has width 1.0."""
+    def widths(v):
+        v = np.asarray(v, dtype=np.float64).ravel()
+        if len(v) < 2:
+            return np.ones(len(v))
+        return np.diff(np.concatenate(([v[0]], 0.5 * (v[:-1] + v[1:]), [v[-1]])))
+
+    dx, dy, dz = widths(xs), widths(ys), widths(zs)
+    return (dx[:, None] * dy[None, :])[:, :, None] * dz[None, None, :]
+
+
+def depth_layers(zs, edges):
+    """Masks of the depth layers [edges[l], edges[l + 1]) of the lattice's ``zs``: {"z lo-hi": mask [1, 1, nz]},
+    which ``posterior_regions`` broadcasts over x and y.  A layer without a node is left out."""
+    zv = np.asarray(zs, dtype=np.float64).ravel()
+    e = np.asarray(edges, dtype=np.float64).ravel()
+    out = {}
+    for lo, hi in zip(e[:-1], e[1:]):
+        mask = (zv >= lo) & (zv < hi)
+        if mask.any():
+            out["z %g-%g" % (lo, hi)] = mask.reshape(1, 1, -1)
+    return out
+
+
+def box_region(xs, ys, zs, lo, hi):
+    """The mask [nx, ny, nz] of the lattice's nodes with lo[a] <= coordinate <= hi[a] on every axis a."""
+    inside = [(np.asarray(v, dtype=np.float64).ravel() >= float(a)) & (np.asarray(v, dtype=np.float64).ravel() <= float(b))
+              for v, a, b in zip((xs, ys, zs), lo, hi)]
+    return inside[0][:, None, None] & inside[1][None, :, None] & inside[2][None, None, :]
+
+
+def region_points(regions, xs, ys, zs, weights="volume"):
+    """``posterior_regions``' regions as one point list: (names, px, py, pz, w or None, reg_off [R + 1]).  A mask
+    gives its nodes in the lattice's order (x fastest) with the voxel weights (``weights="volume"``) or none; a
+    tuple (px, py, pz[, w]) gives its points as they stand, w defaulting to 1.0."""
+    if weights not in ("volume", None):
+        raise ValueError("weights: 'volume' or None")
+    xv, yv, zv = (np.asarray(v, dtype=np.float64).ravel() for v in (xs, ys, zs))
+    shape = (len(xv), len(yv), len(zv))
+    vol = voxel_weights(xv, yv, zv) if weights == "volume" else None
+    names, pts, ws, off = [], [], [], [0]
+    for name, reg in regions.items():
+        if isinstance(reg, tuple):
+            p = [np.asarray(a, dtype=np.float64).ravel() for a in reg[:3]]
+            wr = np.asarray(reg[3], dtype=np.float64).ravel() if len(reg) > 3 else None
+            if not (len(p[0]) == len(p[1]) == len(p[2])) or (wr is not None and len(wr) != len(p[0])):
+                raise ValueError("region %r: px, py, pz and w must have the same length" % (name,))
+        else:
+            mask = np.broadcast_to(np.asarray(reg, dtype=bool), shape)
+            k, j, i = np.nonzero(mask.transpose(2, 1, 0))  # x fastest
+            p = [xv[i], yv[j], zv[k]]
+            wr = vol[i, j, k] if vol is not None else None
+        if len(p[0]) == 0:
+            raise ValueError("region %r holds no point" % (name,))
+        names.append(name)
+        pts.append(p)
+        ws.append(wr)
+        off.append(off[-1] + len(p[0]))
+    if not names:
+        raise ValueError("no region")
+    px, py, pz = (np.concatenate([p[a] for p in pts]) for a in range(3))
+    w = None
+    if any(wr is not None for wr in ws):
+        w = np.concatenate([wr if wr is not None else np.ones(len(p[0])) for wr, p in zip(ws, pts)])
+    return names, px, py, pz, w, np.asarray(off, dtype=np.int64)
+
+
+def posterior_regions(model_hist, dataStruct, TD_parameters, regions, weights="volume", normalize=True,
+                      probs=(0.05, 0.5, 0.95), bins=None, convergence=False, xs=None, ys=None, zs=None):
+    """Questions about regions: is the wedge more attenuating than the back-arc, and with what probability; the
+    lateral average of each depth layer with its credible band; the average along a ray path.  The average of a
+    region is one number per SAMPLE, and its distribution over the samples depends on how the nodes co-vary, so
+    none of this can be read off the per-node maps.  ``regions``: {name: a boolean mask [nx, ny, nz] on the
+    lattice ``xs`` x ``ys`` x ``zs`` (default: dataStruct.xVec / yVec / zVec; anything that broadcasts to it, see
+    ``depth_layers`` and ``box_region``) | a tuple (px, py, pz[, w]) of free points -- a profile, a ray path}.
+    With masks and ``weights="volume"`` a node's weight is its voxel's volume (``voxel_weights``); ``weights=None``
+    gives plain averages; ``normalize=False`` the weighted sums.  -> dict: ``names``, ``series`` [M, R] (shaped
+    for ``posterior_covariance(..., series=...)``), ``weight`` [R], ``mean``, ``std`` [R], ``quantiles`` [nprob,
+    R], ``hist`` [R, nbins + 3] with ``bins`` = (nbins, lo, hi), with ``convergence`` ``rhat``, ``ess``, ``lags``
+    [R], ``greater`` [R, R] (the samples with series[:, a] > series[:, b]) and ``prob_greater`` = greater / M.
+    Same inputs as ``posterior_interfaces`` (Models, nested lists, a ``History`` or a list of them); computed on
+    the device slab by slab (td_rasterize_regions / td_history_regions)."""
+    ctx = context_for(dataStruct)  # (TD_parameters: the siblings' signature)
+    xv, yv, zv = (np.asarray(v if v is not None else d, dtype=np.float64).ravel()
+                  for v, d in ((xs, dataStruct.xVec), (ys, dataStruct.yVec), (zs, dataStruct.zVec)))
+    names, px, py, pz, w, off = region_points(regions, xv, yv, zv, weights)
+    models, lens = _chains(model_hist)
+    if _on_device(models):
+        r = ctx.regions_history(models, px, py, pz, off, w, normalize, probs, bins, convergence)
+    else:
+        r = ctx.regions([m.cells() for m in models], px, py, pz, off, w, normalize, probs, bins,
+                        lens if convergence else None)
+    out = {"names": names, "prob_greater": r["greater"] / np.float64(sum(lens))}
+    for f in ("series", "weight", "mean", "std", "greater") + (("rhat", "ess", "lags") if convergence else ()):
+        out[f] = r[f]
+    if r["quantiles"] is not None:
+        out["quantiles"] = r["quantiles"]
+    if r["hist"] is not None:
+        out["hist"] = r["hist"]
+    return out
+
+
 def posterior_predictive(model_hist, dataStruct, TD_parameters, probs=(0.05, 0.5, 0.95), bins=None, convergence=False,
                          values=False, max_lag=0):
     """Does the ensemble fit the data, ray by ray, and does it predict data it was not fitted to?  Every
