@@ -22,7 +22,7 @@ from .forward import Interpolation, TdContext, context_for, evaluate, v_nearest 
 from .tempering import Exchange, NativeComm, TemperingLadder, decide_swaps, geometric_ladder  # noqa: F401
 from .posterior import (box_region, convergence_maps, credible_maps, depth_layers, model_distributions,  # noqa: F401
                         plot_model_hist, posterior_covariance, posterior_interfaces, posterior_predictive,
-                        posterior_regions, posterior_volume, region_points, section, trace_diagnostics,
-                        voxel_weights)
+                        posterior_regions, posterior_support, posterior_volume, ray_density, region_points, section,
+                        support_weights, trace_diagnostics, voxel_weights)
 from .sharded import RayShardedContext, ray_points, shard_rays, sub_datastruct  # noqa: F401
 from . import jld  # noqa: F401  (save/load model.jld, main_inversion.jl:18)

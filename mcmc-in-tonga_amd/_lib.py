@@ -107,6 +107,25 @@ SIGNATURES_REGIONS = {
     "tdt_regions_plan": (ctypes.c_int, [_i64, _i64, _i64, _i64, _pi64]),
 }
 
+
+class TdSupport(ctypes.Structure):
+    """td_support (include/tdstar_support.h); the arrays and the two optional requests as plain addresses (ptr(),
+    ctypes.addressof)."""
+    _fields_ = [("w", _vp), ("qx", _vp), ("qy", _vp), ("qz", _vp), ("nq", _i64), ("thr", _vp), ("nthr", _i64),
+                ("cell_out", _vp), ("count_out", _vp), ("barren_out", _vp), ("orphans_out", _vp), ("values_out", _vp),
+                ("mean_out", _vp), ("std_out", _vp), ("exceed_out", _vp), ("marg", _vp), ("conv", _vp)]
+
+
+# name -> (restype, argtypes); every symbol declared in include/tdstar_support.h, which tdstar.h does not include
+# (applied by lib() as SIGNATURES is)
+SIGNATURES_SUPPORT = {
+    "td_rasterize_support": (ctypes.c_int, [_vp, _i64, _pi64, _pd, _pd, _pd, _i64, _pi64, ctypes.POINTER(TdSupport)]),
+    "td_history_support": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, ctypes.POINTER(TdSupport)]),
+    "tdt_support_lds_cells": (_i64, []),
+    "tdt_set_support_scatter": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "tdt_support_quantise": (ctypes.c_int, [_pd, _i64, _pi64, _pi64]),
+}
+
 # name -> (restype, argtypes); every symbol declared in include/tdstar.h and include/tdstar_testing.h
 SIGNATURES = {
     "td_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _pd, _pd, _pd, _pd, _pd, _i64, _i64, _pd, _pd]),
@@ -257,7 +276,7 @@ def lib():
                               "(hipcc --offload-arch=gfx950); there is no CPU fallback")
         L = ctypes.CDLL(LIB_PATH)
         older = "TD_LIB_PATH" in os.environ  # (an A/B against an older build: newer testing hooks may be absent)
-        later = dict(SIGNATURES_INTERFACES, **SIGNATURES_REGIONS)  # (the headers of their own)
+        later = dict(SIGNATURES_INTERFACES, **SIGNATURES_REGIONS, **SIGNATURES_SUPPORT)  # (the headers of their own)
         for name, (res, args) in list(SIGNATURES.items()) + list(later.items()):
             if older and (name.startswith("tdt_") or name in later) and not hasattr(L, name):
                 continue

@@ -670,6 +670,97 @@ class TdContext:
 
         return self._regions(call, nm, px, py, pz, reg_off, w, normalize, probs, bins, convergence, max_lag, greater)
 
+    SUP_AUTO, SUP_LDS, SUP_GLOBAL = 0, 1, 2
+
+    @staticmethod
+    def support_lds_cells():
+        """The most cells of a model whose sums ``support``'s scatter kernel keeps in LDS; needs no GPU."""
+        return int(lib().tdt_support_lds_cells())
+
+    def set_support_scatter(self, mode):
+        """How ``support`` adds a model's ray points to its cells: SUP_AUTO, SUP_LDS (in LDS where the model's cells
+        fit ``support_lds_cells()``), SUP_GLOBAL (atomics on the global arrays).  Same answer.  Set it back to
+        SUP_AUTO before ``close``."""
+        check(lib().tdt_set_support_scatter(self.h, int(mode)), self.h)
+
+    def _support(self, call, nmodels, total, w, qx, qy, qz, thresholds, probs, bins, conv, max_lag, want_values,
+                 want_cells):
+        """The td_support request around ``call(byref(req))`` -> dict of the outputs."""
+        wv = f64(np.ravel(w)) if w is not None else None
+        if wv is not None and len(wv) != self.P:
+            raise ValueError("w must have one weight per valid ray point (%d)" % self.P)
+        if qx is None:
+            qx = qy = qz = np.zeros(0)
+        qx, qy, qz = (f64(np.ravel(a)) for a in (qx, qy, qz))
+        nq = len(qx)
+        if not (len(qy) == len(qz) == nq):
+            raise ValueError("qx, qy and qz must have the same length")
+        thr = f64(np.ravel(thresholds))
+        if nq == 0 and (len(thr) or len(np.ravel(probs)) or bins is not None or conv or want_values):
+            raise ValueError("thresholds, probs, bins, convergence and the values need nodes")
+        res = dict(cell=np.empty(total) if want_cells else None,
+                   count=np.empty(total, dtype=np.int64) if want_cells else None, barren=np.empty(nmodels, dtype=np.int64),
+                   orphans=np.empty(nmodels, dtype=np.int64), mean=np.empty(nq) if nq else None,
+                   std=np.empty(nq) if nq else None, values=np.empty((nmodels, nq)) if want_values else None,
+                   exceed=np.empty((len(thr), nq), dtype=np.int64) if len(thr) else None, quantiles=None, hist=None)
+        held = []
+        marg = cw = None
+        if len(np.ravel(probs)) or bins is not None:
+            marg, arrays, res["quantiles"], res["hist"] = self._marginals_want(nq, probs, bins)
+            held.append(arrays)
+        if conv:
+            cw, arrays = self._convergence_want(nq, max_lag, self.CONV_ALL)
+            res.update(arrays)
+        req = _lib.TdSupport(ptr(wv), ptr(qx), ptr(qy), ptr(qz), nq, ptr(thr) if len(thr) else None, len(thr),
+                             ptr(res["cell"]), ptr(res["count"], _lib._pi64), ptr(res["barren"], _lib._pi64),
+                             ptr(res["orphans"], _lib._pi64), ptr(res["values"]), ptr(res["mean"]), ptr(res["std"]),
+                             ptr(res["exceed"], _lib._pi64), ctypes.addressof(marg) if marg is not None else None,
+                             ctypes.addressof(cw) if cw is not None else None)
+        call(ctypes.byref(req))
+        del held
+        return res
+
+    def support(self, models, w=None, qx=None, qy=None, qz=None, thresholds=(), probs=(), bins=None, chain_len=None,
+                max_lag=0, want_values=False, want_cells=True):
+        """td_rasterize_support: which cells, and through them which nodes, this context's rays constrain.  With
+        owner[m][p] the cell ``evaluate`` picks for ray point p (``want_nearest`` order) in model m and ``w`` one
+        weight per point (None: 1.0; quantised once to exact integer multiples of a power of two, so every sum is
+        independent of its order) -> dict(cell[total cells] = the sum of w over the points the cell owns,
+        count[total cells] the points it owns, barren[nmodels] the cells that own none, orphans[nmodels] the points
+        no cell owns; with nodes: mean[nq], std[nq] over the models of U[m][q] = cell[the cell ``rasterize`` picks
+        for node q], values[nmodels, nq] = U or None, exceed[nthr, nq] = the models with U > thresholds[t] or None,
+        quantiles[nprob, nq] or None, hist[nq, nbins + 3] or None, with ``chain_len`` rhat, ess, lags [nq]).
+        ``want_cells=False`` leaves cell and count None (16 bytes per cell of every model stay on the device).
+        models: list of (x, y, z[, zeta]) cell arrays; zeta is not read."""
+        off = np.zeros(len(models) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(m[0]) for m in models])
+        cat = [f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) if len(models) else np.zeros(0)
+               for k in range(3)]
+        lens = np.ascontiguousarray(chain_len, dtype=np.int64).ravel() if chain_len is not None else None
+
+        def call(req):
+            check(lib().td_rasterize_support(self.h, len(models), ptr(off, _lib._pi64), *(ptr(c) for c in cat),
+                                             len(lens) if lens is not None else 0, ptr(lens, _lib._pi64), req), self.h)
+
+        return self._support(call, len(models), int(off[-1]), w, qx, qy, qz, thresholds, probs, bins, lens is not None,
+                             max_lag, want_values, want_cells)
+
+    def support_history(self, histories, w=None, qx=None, qy=None, qz=None, thresholds=(), probs=(), bins=None,
+                        convergence=False, max_lag=0, want_values=False, want_cells=True):
+        """td_history_support: ``support`` on the samples of the histories (chain.History) where they lie, history
+        by history (one without samples is skipped); they may have been recorded on another context of this
+        device.  With ``convergence`` one history is one chain."""
+        histories = list(histories)
+        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
+        counts = [h.count() for h in histories]  # (samples, cells used)
+        nm, total = sum(c[0] for c in counts), sum(c[1] for c in counts)
+
+        def call(req):
+            check(lib().td_history_support(self.h, hs, len(histories), req), self.h)
+
+        return self._support(call, nm, total, w, qx, qy, qz, thresholds, probs, bins, convergence, max_lag, want_values,
+                             want_cells)
+
     def interpolate(self, cells, X, Y, Z, want_nearest=False):
         """-> (zeta[npoints], nearest[npoints] or None)"""
         xc, yc, zc, ze = (f64(c) for c in cells)

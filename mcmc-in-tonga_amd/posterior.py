@@ -407,6 +407,100 @@ def posterior_regions(model_hist, dataStruct, TD_parameters, regions, weights="v
     return out
 
 
+def support_weights(dataStruct, kind="tstar"):
+    """One weight per valid ray point of ``dataStruct`` in ``evaluate``'s ``want_nearest`` order, for
+    ``TdContext.support``: ``"count"`` -> None (every point counts 1); ``"tstar"`` -> g[p], half the sum of
+    rayL * rayU / 1000 of the segments that adjoin the point, so that the sum over the points of g[p] *
+    zeta(owner of p) is the sum of ptS over the rays (MCsub.jl:147-160) and a cell's support is the derivative
+    of the total predicted t* with respect to its zeta; ``"length"`` -> the same with rayL alone, in km."""
+    if kind == "count":
+        return None
+    if kind not in ("tstar", "length"):
+        raise ValueError("kind must be 'count', 'tstar' or 'length'")
+    rayX, rayL, rayU = (np.asarray(a, dtype=np.float64) for a in (dataStruct.rayX, dataStruct.rayL, dataStruct.rayU))
+    out = []
+    for i in range(rayX.shape[1]):
+        nan = np.flatnonzero(np.isnan(rayX[:, i]))
+        c = int(nan[0]) if len(nan) else rayX.shape[0]
+        if c == 0:
+            continue
+        seg = rayL[:c - 1, i] * rayU[:c - 1, i] / 1000.0 if kind == "tstar" else rayL[:c - 1, i].copy()
+        out.append(0.5 * (np.concatenate((seg, [0.0])) + np.concatenate(([0.0], seg))))
+    return np.concatenate(out) if out else np.zeros(0)
+
+
+def _lattice(dataStruct, xs, ys, zs):
+    """(xv, yv, zv, the shape x fastest, qx, qy, qz) of the lattice ``posterior_volume`` sweeps."""
+    xv, yv, zv = (np.asarray(v if v is not None else d, dtype=np.float64).ravel()
+                  for v, d in ((xs, dataStruct.xVec), (ys, dataStruct.yVec), (zs, dataStruct.zVec)))
+    qx = np.tile(xv, len(yv) * len(zv))
+    qy = np.tile(np.repeat(yv, len(xv)), len(zv))
+    qz = np.repeat(zv, len(xv) * len(yv))
+    return xv, yv, zv, (len(zv), len(yv), len(xv)), qx, qy, qz
+
+
+def posterior_support(model_hist, dataStruct, TD_parameters, weights="tstar", thresholds=(0.0,), probs=None, bins=None,
+                      convergence=False, xs=None, ys=None, zs=None):
+    """Did the data say anything about this node, or is it the prior?  A Voronoi cell that owns no ray point does
+    not enter ``evaluate``: its zeta is a prior draw in every sample.  Per sample, every cell's support is the sum
+    of ``weights`` (a kind of ``support_weights``, an array of one weight per valid ray point, or None: a count)
+    over the ray points it owns, and a node's support is its owning cell's.  On the lattice ``xs`` x ``ys`` x
+    ``zs`` (default: dataStruct.xVec / yVec / zVec) -> dict of [nx, ny, nz] arrays ``mean``, ``std`` of the node
+    support over the samples, ``share`` [nthr, ...] the share of the samples whose support exceeds thresholds[t]
+    (0.0: the node's cell touches the data at all), ``exceed`` the raw counts, ``quantiles`` [nprob, ...],
+    ``hist`` [..., nbins + 3], with ``convergence`` ``rhat``, ``ess``, ``lags``; per sample ``barren`` (cells that
+    own no ray point), ``orphans`` (ray points no cell owns), ``cells`` and ``barren_share`` = barren / cells: the
+    part of nCells that is not structure; ``x``, ``y``, ``z``, ``thresholds``.  Same inputs as ``posterior_volume``
+    (Models, nested lists, a ``History`` or a list of them); computed on the device slab by slab
+    (td_rasterize_support / td_history_support)."""
+    ctx = context_for(dataStruct)  # (TD_parameters: the siblings' signature; the lattice decides everything here)
+    xv, yv, zv, shape, qx, qy, qz = _lattice(dataStruct, xs, ys, zs)
+    w = support_weights(dataStruct, weights) if isinstance(weights, str) else weights
+    thr = np.asarray(thresholds, dtype=np.float64).ravel()
+    probs = () if probs is None else probs
+    models, lens = _chains(model_hist)
+    if _on_device(models):
+        r = ctx.support_history(models, w, qx, qy, qz, thr, probs, bins, convergence, want_cells=False)
+        cells = np.concatenate([h.traces()[:, 1] for h in models]).astype(np.int64)
+    else:
+        r = ctx.support([m.cells() for m in models], w, qx, qy, qz, thr, probs, bins, lens if convergence else None,
+                        want_cells=False)
+        cells = np.array([len(m.cells()[0]) for m in models], dtype=np.int64)
+    M = sum(lens)
+
+    def grid(a):  # [..., nq] -> [..., nx, ny, nz]
+        lead = a.shape[:-1]
+        k = len(lead)
+        return a.reshape(lead + shape).transpose(tuple(range(k)) + (k + 2, k + 1, k)).copy()
+
+    out = {"x": xv, "y": yv, "z": zv, "thresholds": thr, "barren": r["barren"], "orphans": r["orphans"], "cells": cells}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["barren_share"] = r["barren"] / cells.astype(np.float64)
+    for f in ("mean", "std") + (("rhat", "ess", "lags") if convergence else ()):
+        out[f] = grid(r[f])
+    out["exceed"] = grid(r["exceed"]) if r["exceed"] is not None else np.empty((0,) + shape[::-1], dtype=np.int64)
+    out["share"] = out["exceed"] / np.float64(M)
+    if r["quantiles"] is not None:
+        out["quantiles"] = grid(r["quantiles"])
+    if r["hist"] is not None:
+        out["hist"] = r["hist"].reshape(shape + (r["hist"].shape[1],)).transpose(2, 1, 0, 3).copy()
+    return out
+
+
+def ray_density(dataStruct, xs=None, ys=None, zs=None, weights="length"):
+    """The classical ray-density map: every valid ray point of ``dataStruct`` gives its weight (a kind of
+    ``support_weights``, an array, or None: a count) to the nearest node of the lattice ``xs`` x ``ys`` x ``zs``
+    (default: dataStruct.xVec / yVec / zVec) -- one ``TdContext.support`` call with a single model whose cells are
+    the nodes.  -> dict(``density`` [nx, ny, nz], ``count`` [nx, ny, nz], ``orphans``: the points farther than the
+    search's sentinel from every node, ``x``, ``y``, ``z``)."""
+    ctx = context_for(dataStruct)
+    xv, yv, zv, shape, qx, qy, qz = _lattice(dataStruct, xs, ys, zs)
+    w = support_weights(dataStruct, weights) if isinstance(weights, str) else weights
+    r = ctx.support([(qx, qy, qz)], w)
+    return {"x": xv, "y": yv, "z": zv, "density": r["cell"].reshape(shape).transpose(2, 1, 0).copy(),
+            "count": r["count"].reshape(shape).transpose(2, 1, 0).copy(), "orphans": int(r["orphans"][0])}
+
+
 def posterior_predictive(model_hist, dataStruct, TD_parameters, probs=(0.05, 0.5, 0.95), bins=None, convergence=False,
                          values=False, max_lag=0):
     """Does the ensemble fit the data, ray by ray, and does it predict data it was not fitted to?  Every
