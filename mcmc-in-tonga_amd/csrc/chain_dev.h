@@ -56,6 +56,9 @@ struct ChainScalars {
                                // cycles, terms added one by one
                                // [35] / [45] deaths / changes on the short road, [55] guesses adopted with the
                                // barren flag up, [25] of those the ones cleared at adoption
+                               // two counts to a slot, 32 bits each: [7] / [75] deaths / changes whose count was
+                               // read at the loop top, low: it owned no point, high: it owned some; the high
+                               // halves of [35] / [45]: deaths / changes on the full path that owned no point
     int ncells;            // cells in the model
     int nslots;            // slot high-water mark
     int nfree;             // free-slot stack depth

@@ -490,6 +490,7 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
         if (!RLDS) sh.dsum = sh.dabs = 0.0;
         sh.grid_fallbacks32 = 0;
         sh.e_done = sh.b_done = 0;
+        if constexpr (kNoBarB) sh.q_done = 0;
         geo_fill(sh.geo, d);
         for (int a = 0; a < 5; ++a) sh.proposed[a] = sh.accepted[a] = 0;
         sh.phi = s0.phi;
@@ -692,13 +693,40 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
         int pre_q = 0, pre_ray = 0, pre_s = 0;
         double pre_bd = 0.0, pre_x = 0.0, pre_y = 0.0, pre_z = 0.0;
         // The short road (block-uniform; free-running instances): a change or death whose cell owns no ray
-        // point (PState::barren, trusted) changes no point and no ray -- no tile pass, no b_done hand-off, no
+        // point changes no point and no ray -- no tile pass, no b_done hand-off, no
         // phases C-E; every counter stays 0 and k0 == n, so phase F decides on phi_n = phi_r as it does for any
         // proposal that turned out empty, and phase G's loops are empty.  A death keeps its killed-site query
-        // and phase B's barrier (the decision reads the answer after it); a change goes straight to phase F,
-        // whose barrier is then the one between the loop top's reads and wave 0's end-of-iteration writes.
-        const bool sroad = !SCRIPT && cur.barren != 0 && p.active && p.valid && P.debug_prior != 1 &&
-                           (action == tdchain::kChange || action == tdchain::kDeath);
+        // and (rays in HBM, 4 waves) phase B's barrier, after which the decision reads the answer; a change
+        // goes straight to phase F, whose barrier is then the one between the loop top's reads and wave 0's
+        // end-of-iteration writes -- and so does the LDS layout's death (qroad, below).
+        // Whether the cell owns a point: PState::barren when the guess that read the count was adopted
+        // untouched; else (a launch's first proposal, every 64th, one wave 0 made at the last iteration's end)
+        // every wave reads DevChain::own here for itself -- one wave-uniform address, an agent-scope load
+        // served by L2 as phase F's, no LDS word and no barrier.  The answer is the same in every wave: own's
+        // only writers are phase G's commit atomics, each waited for by its wave before the iteration-end
+        // barrier this wave has just passed, and the next ones come after this iteration's phase F barrier;
+        // at a launch's start the count is the launch-boundary invariant (tdt_chain_own_check).
+        bool sroad = false;
+        int own_top = -1;  // the count read here (>= 0), or not asked
+        if constexpr (!SCRIPT) {
+            // (the action first, what the registers hold: a birth or a move waits for nothing here; debug_prior,
+            // a load, last and beside the count's)
+            if ((action == tdchain::kChange || action == tdchain::kDeath) && p.active && p.valid) {
+                const bool up = cur.barren != 0;
+                if (!up)
+                    own_top = __builtin_amdgcn_readfirstlane(
+                        __hip_atomic_load((const __attribute__((address_space(1))) int *)(d.own + slot_k),
+                                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                sroad = (up || own_top == 0) && P.debug_prior != 1;
+            }
+        }
+        // LDS layout: the short road's death takes no barrier before phase F either.  Only wave 0's decision
+        // reads the killed-site query's answer: the query wave publishes it (q_zeta, then q_done) and wave 0
+        // waits for the flag just before it decides, while phase F's side work -- tid 64's guess, the grid
+        // prefetch (on wave kWv - 3: the last wave is asking), the shift edges -- starts at the loop top.
+        // Phase F's barrier is then the one between the loop top's reads and wave 0's end-of-iteration writes,
+        // as for the short road's change.
+        const bool qroad = kNoBarB && sroad && action == tdchain::kDeath;
         if (p.active) {
             // ============ phase B: tile pass || birth/death Interpolation ============
             // (a scripted step brings its own values: no Interpolation query -- but for a server's death
@@ -891,6 +919,11 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
                 const Nearest r = wave_nearest(d, v, sh, lane, birth ? p.x : kx, birth ? p.y : ky, birth ? p.z : kz,
                                                birth ? -1 : slot_k, -1, 0.0, 0.0, 0.0, 0.0);
                 if (lane == 0) sh.q_zeta = r.z;
+                if (qroad) {  // (no barrier follows: the answer released before the flag wave 0 acquires)
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    if (lane == 0) atomicAdd(&sh.q_done, 1);
+                    SKEW(22);
+                }
             }
         }
         // Phase B's barrier (tile list complete, query answered) -- taken by an inactive proposal too (a birth
@@ -901,7 +934,8 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
         // NEXT proposal.  So every iteration has a block barrier between the loop top and wave 0's
         // end-of-iteration writes (this one, or C's and F's).  Found by the wave-skew build
         // (tools/skew_probe.py, the 8-cell model at max_cells 12).
-        if (!nobar && !(sroad && action == tdchain::kChange)) {  // (the short road's change: phase F's barrier)
+        // (the short road's change, and its death in the LDS layout: phase F's barrier)
+        if (!nobar && !(sroad && action == tdchain::kChange) && !qroad) {
             __syncthreads();
             SKEW(4);
             if (p.active && action == tdchain::kBirth) czeta = sh.q_zeta;
@@ -1457,6 +1491,11 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
                     }
                 }
                 if (prof_on && lane == 0) sh.prof[66] += clock64() - tF;  // diagnostic: scan done
+                if (qroad) {  // the query wave's answer (no barrier since the loop top)
+                    SPIN_WAIT(__hip_atomic_load(&sh.q_done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < 1,
+                              1000000000);
+                    zetanew_death = sh.q_zeta;
+                }
             }
             if (tid == 0) {
                 // Metropolis-Hastings decision (on bounds: the one accept() gives on the exact values);
@@ -1493,15 +1532,26 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
                                         d.free_slots, d.cx, d.cy, d.cz, d.czeta, [&](int pos) { return v.ord[pos]; }, d.own);
                     sh.spec_ok = 1;
                 }
-            } else if (wv == kWv - 1 || (kWv >= 6 && wv == kWv - 2)) {
-                // wave kWv - 1: the grid data an accepted update will need; wave kWv - 2 (with 8 waves;
-                // with 4 the last wave after its prefetch): accounting and the model-size factors
-                if (wv == kWv - 1)
+            } else if (wv == kWv - 1 || (kWv >= 6 && wv == kWv - 2) || (qroad && wv == kWv - 3)) {
+                // wave kWv - 1: the grid data an accepted update will need (the LDS layout's short-road death:
+                // wave kWv - 3, which has no tile to refresh -- the last wave comes here from its query with
+                // nothing left to do); wave kWv - 2 (with 8 waves; with 4 the last wave after its prefetch):
+                // accounting and the model-size factors
+                if (wv == (qroad ? kWv - 3 : kWv - 1))
                     grid_prefetch(d, sh, lane, action, action == tdchain::kBirth ? new_slot : slot_k, kx, ky,
                                   kz, pp.x, pp.y, pp.z);
                 if (wv == (kWv >= 6 ? kWv - 2 : kWv - 1)) {
                     if (prof_on && lane == 0) {  // diagnostic: work sizes
                         if (sroad) sh.prof[action == tdchain::kDeath ? 35 : 45] += 1;  // the short road, by action
+                        // counts read at the loop top, by action ([7] deaths, [75] changes) and by answer: "owns
+                        // none" in the low 32 bits, "owns points" in the high
+                        if (own_top >= 0 && fwd)
+                            sh.prof[action == tdchain::kDeath ? 7 : 75] += own_top == 0 ? 1ll : 1ll << 32;
+                        // a change or death that turned out to own no point and took the full path all the same
+                        // (none, once every unknown count is read at the loop top): the high 32 bits of [35] / [45]
+                        if (!SCRIPT && fwd && !sroad &&
+                            ((action == tdchain::kChange && sh.n_changed == 0) || (action == tdchain::kDeath && no == 0)))
+                            sh.prof[action == tdchain::kDeath ? 35 : 45] += 1ll << 32;
                         sh.prof[68] += sh.n_tiles;
                         sh.prof[69] += sh.pts_seen;
                         sh.prof[70] += sh.n_changed;
@@ -1842,7 +1892,7 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
                         // Its barren flag holds what own[] said in phase F, before this iteration's commit: it
                         // stays only if the commit moved no owner -- a rejection, an accepted change, or an
                         // accepted proposal that changed no point (a kept guess follows nothing else but a
-                        // move).  Else the proposal takes the full path, which is right whatever the flag.
+                        // move).  Else the count is not known: the proposal reads it at the loop top.
                         // (The flag is not read here: cleared whether up or not, off the common path.)
                         if (prof_on && g.barren) sh.prof[55] += 1;  // diagnostic: guesses adopted with the flag up
                         if (acc && action != tdchain::kChange && sh.gs.nc != 0) {
@@ -1879,6 +1929,7 @@ __global__ __launch_bounds__(NTH, 2) void k_chain_run(const DevChain *__restrict
                     sh.n_super[(it + 1) & 1] = 0;  // the other parity's list is refreshed first
                     sh.pts_seen = sh.ray_pts = 0;
                     sh.e_done = sh.b_done = 0;
+                    if constexpr (kNoBarB) sh.q_done = 0;
                     sh.k0 = n;
                 }
             }

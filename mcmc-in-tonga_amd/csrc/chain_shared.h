@@ -79,8 +79,11 @@ struct PState {
     int slot_k, new_slot, eval;
     // the selected cell owned no ray point (DevChain::own) when the proposal was made AND nothing can have
     // changed ownership since: set only on a guess of phase F, cleared at its adoption unless the iteration
-    // it was made in left every owner alone (k_chain_run, the iteration's end).  A change or death with it
-    // set changes no ray: it takes the short road (no tile pass, no phases C-E)
+    // it was made in left every owner alone (k_chain_run, the iteration's end).  Down, it says nothing (the
+    // guess read a count above 0, or was cleared; a proposal wave 0 makes at an iteration's end, and a
+    // launch's first, never asked): a free-running change or death then reads the count at the loop top.  A
+    // change or death whose cell owns no point changes no ray: it takes the short road (no tile pass, no
+    // phases C-E)
     int barren;
 };
 
@@ -151,8 +154,7 @@ struct Shared {
     int n_super[2];  // rays in HBM: super-tiles hit, by iteration parity (the next iteration refreshes their maxima)
     int pts_seen, ray_pts;
     int e_done;  // LDS layout: waves done with their phase-E rays (waves 1..; wave 0 waits for them)
-    int b_done;  // LDS layout: waves done with their phase-B tile pass (phase B without its barrier)
-    // bucket-grid update of an accepted proposal (applied by the last wave in phase G)
+    int b_done;  // LDS layout: waves done with their phase-B tile pass (phase B without its barrier)    // bucket-grid update of an accepted proposal (applied by the last wave in phase G)
     int g_op, g_slot;           // bit 1: remove at old site, bit 2: insert at new site, bit 4: new value in place
     // what the update needs from the grid, read during phase F (G only writes)
     int gp_bo, gp_co, gp_pos, gp_bn, gp_cn;
@@ -196,6 +198,10 @@ struct Shared {
     int shift_done;
     int shift_edge[kChainThreads / 64];
     int dbg_site[kChainThreads / 64];  // the skew build's trail: each wave's last skew site (SKEW)
+    // LDS layout, free-running: a short-road death's killed-site query is answered (q_zeta): raised by the
+    // query wave, waited for by wave 0 before it decides, cleared with e_done and b_done.  (Last, in what was
+    // padding: every other offset, and the block's size in 16-byte units, stay what they were.)
+    int q_done;
 };
 
 // LDS carve-up (host and device agree on it through this function).

@@ -71,13 +71,19 @@ def main():
     res["chi2 scan rounds per proposal"] = round((out[65] - out0[65]) / ev, 2)
     res["per evaluated proposal: tiles hit, points seen, points changed, rays changed"] = [
         round((out[k] - out0[k]) / ev, 1) for k in (68, 69, 70, 71)]
-    short = [int(out[k] - out0[k]) for k in (35, 45)]
+    lo, hi = (lambda k: int(out[k] - out0[k]) & 0xffffffff), (lambda k: int(out[k] - out0[k]) >> 32)  # two counts a slot
+    short = [lo(k) for k in (35, 45)]
     res["short road (the cell owns no ray point): deaths, changes, share of all proposals"] = short + [
         round(sum(short) / ev, 4)]
+    res["point counts read at the loop top: deaths owning none / some, changes owning none / some"] = [
+        lo(7), hi(7), lo(75), hi(75)]
+    barren_full = [hi(k) for k in (35, 45)]
+    res["on the full path though the cell owned no point: deaths, changes, share of all proposals"] = barren_full + [
+        round(sum(barren_full) / ev, 4)]
     res["guesses adopted with a barren cell, of those with the flag cleared at adoption"] = [
         int(out[k] - out0[k]) for k in (55, 25)]
-    res["chi2 walk (rays in HBM) per proposal: events, batch-load cycles, walk cycles, terms one by one"] = [
-        round((out[k] - out0[k]) / ev, 1) for k in (72, 73, 74, 75)]
+    res["chi2 walk (rays in HBM) per proposal: events, batch-load cycles, walk cycles"] = [
+        round((out[k] - out0[k]) / ev, 1) for k in (72, 73, 74)]
     res["F wave 0: cycles to scan end / to decision (per iter)"] = [round((out[k] - out0[k]) / iters, 1)
                                                                      for k in (66, 67)]
     print(json.dumps(res, indent=1))
