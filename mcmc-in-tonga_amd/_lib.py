@@ -126,6 +126,23 @@ SIGNATURES_SUPPORT = {
     "tdt_support_quantise": (ctypes.c_int, [_pd, _i64, _pi64, _pi64]),
 }
 
+
+class TdRecovery(ctypes.Structure):
+    """td_recovery (include/tdstar_recovery.h); the arrays and the two optional requests as plain addresses (ptr(),
+    ctypes.addressof)."""
+    _fields_ = [("px", _vp), ("py", _vp), ("pz", _vp), ("w", _vp), ("np", _i64), ("reg_off", _vp), ("nreg", _i64),
+                ("truth", _vp), ("normalize", _i64), ("below_out", _vp), ("equal_out", _vp), ("above_out", _vp),
+                ("dmean_out", _vp), ("dstd_out", _vp), ("series_out", _vp), ("weight_out", _vp), ("mean_out", _vp),
+                ("std_out", _vp), ("marg", _vp), ("conv", _vp)]
+
+
+# name -> (restype, argtypes); every symbol declared in include/tdstar_recovery.h, which tdstar.h does not include
+# (applied by lib() as SIGNATURES is)
+SIGNATURES_RECOVERY = {
+    "td_rasterize_recovery": (ctypes.c_int, [_vp, _i64, _pi64, _pd, _pd, _pd, _pd, _i64, _pi64, ctypes.POINTER(TdRecovery)]),
+    "td_history_recovery": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, ctypes.POINTER(TdRecovery)]),
+}
+
 # name -> (restype, argtypes); every symbol declared in include/tdstar.h and include/tdstar_testing.h
 SIGNATURES = {
     "td_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _pd, _pd, _pd, _pd, _pd, _i64, _i64, _pd, _pd]),
@@ -276,7 +293,7 @@ def lib():
                               "(hipcc --offload-arch=gfx950); there is no CPU fallback")
         L = ctypes.CDLL(LIB_PATH)
         older = "TD_LIB_PATH" in os.environ  # (an A/B against an older build: newer testing hooks may be absent)
-        later = dict(SIGNATURES_INTERFACES, **SIGNATURES_REGIONS, **SIGNATURES_SUPPORT)  # (the headers of their own)
+        later = dict(SIGNATURES_INTERFACES, **SIGNATURES_REGIONS, **SIGNATURES_SUPPORT, **SIGNATURES_RECOVERY)  # (the headers of their own)
         for name, (res, args) in list(SIGNATURES.items()) + list(later.items()):
             if older and (name.startswith("tdt_") or name in later) and not hasattr(L, name):
                 continue

@@ -670,6 +670,81 @@ class TdContext:
 
         return self._regions(call, nm, px, py, pz, reg_off, w, normalize, probs, bins, convergence, max_lag, greater)
 
+    def _recovery(self, call, nmodels, px, py, pz, truth, reg_off, w, normalize, probs, bins, conv, max_lag):
+        """The td_recovery request around ``call(byref(req))`` -> dict of the outputs."""
+        px, py, pz, tr = (f64(np.ravel(a)) for a in (px, py, pz, truth))
+        npts = len(px)
+        if not (len(py) == len(pz) == len(tr) == npts):
+            raise ValueError("px, py, pz and truth must have the same length")
+        wv = f64(np.ravel(w)) if w is not None else None
+        if wv is not None and len(wv) != npts:
+            raise ValueError("w must have one weight per point")
+        off = (np.ascontiguousarray(reg_off, dtype=np.int64).ravel() if reg_off is not None
+               else np.array([0, npts], dtype=np.int64))
+        R = len(off) - 1
+        if R < 1:
+            raise ValueError("reg_off must hold nreg + 1 >= 2 offsets")
+        res = dict(below=np.empty(npts, dtype=np.int64), equal=np.empty(npts, dtype=np.int64),
+                   above=np.empty(npts, dtype=np.int64), dmean=np.empty(npts), dstd=np.empty(npts),
+                   series=np.empty((nmodels, R)), weight=np.empty(R), mean=np.empty(R), std=np.empty(R), quantiles=None,
+                   hist=None)
+        held = []
+        marg = cw = None
+        if len(np.ravel(probs)) or bins is not None:
+            marg, arrays, res["quantiles"], res["hist"] = self._marginals_want(R, probs, bins)
+            held.append(arrays)
+        if conv:
+            cw, arrays = self._convergence_want(R, max_lag, self.CONV_ALL)
+            res.update(arrays)
+        i64 = _lib._pi64
+        req = _lib.TdRecovery(ptr(px), ptr(py), ptr(pz), ptr(wv), npts, ptr(off, i64), R, ptr(tr), int(bool(normalize)),
+                              ptr(res["below"], i64), ptr(res["equal"], i64), ptr(res["above"], i64), ptr(res["dmean"]),
+                              ptr(res["dstd"]), ptr(res["series"]), ptr(res["weight"]), ptr(res["mean"]), ptr(res["std"]),
+                              ctypes.addressof(marg) if marg is not None else None,
+                              ctypes.addressof(cw) if cw is not None else None)
+        call(ctypes.byref(req))
+        del held
+        return res
+
+    def recovery(self, models, px, py, pz, truth, reg_off=None, w=None, normalize=True, probs=(), bins=None,
+                 chain_len=None, max_lag=0):
+        """td_rasterize_recovery: the models against a known model whose value at point p is ``truth[p]``.  The
+        points, the regions (``reg_off=None``: all points are one region) and the weights are ``regions``'.  With
+        V[m][p] the nearest-cell value of model m at point p (``volume``'s) and D = V - truth -> dict(below[np],
+        equal[np], above[np] = the models with V <, ==, > truth (a NaN V counts in none); dmean[np], dstd[np] the
+        mean and sigma of D over the models (``rasterize``'s); series[nmodels, R] = the sum over the region of w[p]
+        * (D * D) in ``rasterize``'s association over the index within the region, divided by weight[R] when
+        ``normalize``: the weighted mean square distance of every model to the truth; mean[R], std[R], quantiles
+        [nprob, R] or None, hist[R, nbins + 3] or None and, with ``chain_len``, rhat, ess, lags [R] of the series, as
+        ``regions`` gives them).  Any number of points, swept slab by slab as by ``volume``.  models as for
+        ``rasterize``."""
+        off = np.zeros(len(models) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(m[0]) for m in models])
+        cat = [f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) if len(models) else np.zeros(0)
+               for k in range(4)]
+        lens = np.ascontiguousarray(chain_len, dtype=np.int64).ravel() if chain_len is not None else None
+
+        def call(req):
+            check(lib().td_rasterize_recovery(self.h, len(models), ptr(off, _lib._pi64), *(ptr(c) for c in cat),
+                                              len(lens) if lens is not None else 0, ptr(lens, _lib._pi64), req), self.h)
+
+        return self._recovery(call, len(models), px, py, pz, truth, reg_off, w, normalize, probs, bins, lens is not None,
+                              max_lag)
+
+    def recovery_history(self, histories, px, py, pz, truth, reg_off=None, w=None, normalize=True, probs=(), bins=None,
+                         convergence=False, max_lag=0):
+        """td_history_recovery: ``recovery`` on the samples of the histories (chain.History) where they lie, history
+        by history (one without samples is skipped); they may have been recorded on another context of this
+        device.  With ``convergence`` one history is one chain."""
+        histories = list(histories)
+        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
+        nm = sum(len(h) for h in histories)
+
+        def call(req):
+            check(lib().td_history_recovery(self.h, hs, len(histories), req), self.h)
+
+        return self._recovery(call, nm, px, py, pz, truth, reg_off, w, normalize, probs, bins, convergence, max_lag)
+
     SUP_AUTO, SUP_LDS, SUP_GLOBAL = 0, 1, 2
 
     @staticmethod

@@ -7,9 +7,12 @@ an nx x nz matrix, xs fastest), then takes the mean and standard deviation
 over the models and masks nodes whose std exceeds 5.  Here the model sweep
 and both statistics run on the GPU (td_rasterize); plotting is out of scope.
 """
+import dataclasses
+
 import numpy as np
 
-from .forward import context_for
+from .defstruct import Model
+from .forward import context_for, evaluate
 
 
 def _flatten(model_hist):
@@ -499,6 +502,134 @@ def ray_density(dataStruct, xs=None, ys=None, zs=None, weights="length"):
     r = ctx.support([(qx, qy, qz)], w)
     return {"x": xv, "y": yv, "z": zv, "density": r["cell"].reshape(shape).transpose(2, 1, 0).copy(),
             "count": r["count"].reshape(shape).transpose(2, 1, 0).copy(), "orphans": int(r["orphans"][0])}
+
+
+def checkerboard_model(xs, ys, zs, blocks, lo, hi):
+    """The known model of a checkerboard test: a ``Model`` whose nuclei are the centres of a regular ``blocks`` =
+    (bx, by, bz) division of the box of the lattice ``xs`` x ``ys`` x ``zs`` (cell i + bx (j + by k), x fastest),
+    zeta = ``lo`` where i + j + k is even and ``hi`` where it is odd.  The nuclei are equally spaced along every
+    axis, so the Voronoi cells are the blocks; a point on a face goes to the lower index, as everywhere."""
+    bx, by, bz = (int(b) for b in blocks)
+    if min(bx, by, bz) < 1:
+        raise ValueError("blocks: at least one block along every axis")
+    centres = []
+    for v, b in zip((xs, ys, zs), (bx, by, bz)):
+        v = np.asarray(v, dtype=np.float64).ravel()
+        a, width = float(v.min()), (float(v.max()) - float(v.min())) / b
+        centres.append(a + (np.arange(b) + 0.5) * width)
+    k, j, i = np.meshgrid(np.arange(bz), np.arange(by), np.arange(bx), indexing="ij")
+    i, j, k = i.ravel(), j.ravel(), k.ravel()
+    zeta = np.where((i + j + k) % 2 == 0, float(lo), float(hi))
+    return Model(float(bx * by * bz), centres[0][i], centres[1][j], centres[2][k], zeta)
+
+
+def synthetic_data(dataStruct, model, TD_parameters, noise=1.0, seed=0):
+    """The data a known model would have given: a copy of ``dataStruct`` with tS = ptS(model) + noise * allSig *
+    N(0, 1), ptS being ``evaluate``'s prediction on the rays of ``dataStruct`` and the draws
+    numpy.random.default_rng(seed)'s.  ``noise=0`` gives the exact data.  Neither input is modified; the copy gets
+    a device context of its own on first use."""
+    prm = TD_parameters.replace(debug_prior=0) if TD_parameters.debug_prior == 1 else TD_parameters
+    m, _, valid = evaluate(model.copy(), dataStruct, prm)
+    if valid != 1:
+        raise ValueError("the model cannot be evaluated on these rays")
+    pt = np.asarray(m.ptS, dtype=np.float64).ravel()
+    sig = np.asarray(dataStruct.allSig, dtype=np.float64).ravel()
+    draws = np.random.default_rng(seed).standard_normal(len(pt))
+    tS = pt + (float(noise) * sig) * draws
+    return dataclasses.replace(dataStruct, tS=tS.reshape(np.shape(dataStruct.tS)), _td_ctx=None)
+
+
+def posterior_recovery(model_hist, dataStruct, TD_parameters, truth, regions=None, weights="volume", band=(0.05, 0.95),
+                       probs=(0.05, 0.5, 0.95), bins=None, convergence=False, xs=None, ys=None, zs=None):
+    """The ensemble against a model that is KNOWN: a checkerboard or spike test, a synthetic recovery, another
+    study's volume.  ``truth``: a ``Model`` (rasterised on the lattice ``xs`` x ``ys`` x ``zs``, default
+    dataStruct.xVec / yVec / zVec, by the nearest search of the samples) or an array [nx, ny, nz] of node values.
+    ``regions`` as in ``posterior_regions`` (default: one region "all" of every node, with ``voxel_weights`` when
+    ``weights="volume"``); free points need a ``Model`` as the truth.  -> dict, per node [nx, ny, nz]: ``truth``;
+    ``bias``, ``std`` (the mean and sigma over the samples of zeta - truth), ``zscore`` = bias / std; ``below``,
+    ``equal``, ``above`` (the samples with zeta <, ==, > truth); ``pit`` = (below + 0.5 equal) / M, the mid-rank
+    probability integral transform; ``inside`` = band[0] <= pit <= band[1]; ``pit_hist``: ten equal bins of pit
+    over the nodes (flat when the ensemble is calibrated).  Per region: ``names``, ``weight`` [R], ``coverage``
+    [R], the weighted share of the region's points that are inside; ``msd`` [M, R], every sample's weighted mean
+    square distance to the truth, ``rms`` = sqrt(msd) with ``rms_mean``, ``rms_std``, ``rms_quantiles`` [nprob, R]
+    (numpy on the M x R matrix); the device's statistics of msd ``msd_mean``, ``msd_std``, ``msd_quantiles``,
+    ``msd_hist`` [R, nbins + 3] with ``bins`` = (nbins, lo, hi) in msd's units and, with ``convergence``, ``rhat``,
+    ``ess``, ``lags`` [R] and ``summary`` as in ``convergence_maps`` (R-hat is that of the msd trace: burn-in in
+    model space); ``mean_model_rms`` [R] = sqrt(sum w bias^2 / W), the distance of the MEAN model, which with
+    weights >= 0 is never above the root of msd_mean.  Same inputs as ``posterior_regions``; computed on the device slab by slab
+    (td_rasterize_recovery / td_history_recovery).  With ``regions`` given the per-node outputs come from one more
+    region that lists every node once."""
+    ctx = context_for(dataStruct)  # (TD_parameters: the siblings' signature)
+    xv, yv, zv, shape, qx, qy, qz = _lattice(dataStruct, xs, ys, zs)
+    nq = len(qx)
+    vol = voxel_weights(xv, yv, zv).transpose(2, 1, 0).ravel() if weights == "volume" else None
+    if weights not in ("volume", None):
+        raise ValueError("weights: 'volume' or None")
+    if regions is None:
+        names, px, py, pz, w, off = ["all"], qx, qy, qz, vol, np.array([0, nq], dtype=np.int64)
+    else:  # the named regions, then every node once
+        names, px, py, pz, w, off = region_points(regions, xv, yv, zv, weights)
+        if w is not None or vol is not None:
+            w = np.concatenate((w if w is not None else np.ones(len(px)), vol if vol is not None else np.ones(nq)))
+        px, py, pz = np.concatenate((px, qx)), np.concatenate((py, qy)), np.concatenate((pz, qz))
+        off = np.concatenate((off, [off[-1] + nq]))
+    R = len(names)
+    if isinstance(truth, Model):
+        tp = ctx.rasterize([truth.cells()], px, py, pz, want_values=True)[2][0]
+    else:
+        tn = np.asarray(truth, dtype=np.float64)
+        if tn.shape != (len(xv), len(yv), len(zv)):
+            raise ValueError("truth: a Model or an array [nx, ny, nz]")
+        parts = []
+        for name, reg in (regions or {}).items():  # (region_points' order)
+            if isinstance(reg, tuple):
+                raise ValueError("region %r: free points need a Model as the truth" % (name,))
+            parts.append(tn.transpose(2, 1, 0)[np.broadcast_to(np.asarray(reg, dtype=bool), tn.shape).transpose(2, 1, 0)])
+        tp = np.concatenate(parts + [tn.transpose(2, 1, 0).ravel()])
+    models, lens = _chains(model_hist)
+    if _on_device(models):
+        r = ctx.recovery_history(models, px, py, pz, tp, off, w, True, probs, bins, convergence)
+    else:
+        r = ctx.recovery([m.cells() for m in models], px, py, pz, tp, off, w, True, probs, bins,
+                         lens if convergence else None)
+    M = sum(lens)
+
+    def grid(a):  # the last nq listed points -> [nx, ny, nz]
+        return a[-nq:].reshape(shape).transpose(2, 1, 0).copy()
+
+    pit_p = (r["below"] + 0.5 * r["equal"]) / np.float64(M)  # per listed point
+    inside_p = (band[0] <= pit_p) & (pit_p <= band[1])
+    wp = w if w is not None else np.ones(len(px))
+    out = {"x": xv, "y": yv, "z": zv, "names": names, "truth": grid(tp), "bias": grid(r["dmean"]), "std": grid(r["dstd"]),
+           "below": grid(r["below"]), "equal": grid(r["equal"]), "above": grid(r["above"]), "pit": grid(pit_p),
+           "inside": grid(inside_p), "weight": r["weight"][:R], "msd": r["series"][:, :R].copy()}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["zscore"] = out["bias"] / out["std"]
+        out["pit_hist"] = np.histogram(out["pit"], bins=10, range=(0.0, 1.0))[0]
+        out["coverage"] = np.array([np.sum(wp[a:b] * inside_p[a:b]) / np.sum(wp[a:b]) for a, b in zip(off[:R], off[1:R + 1])])
+        out["mean_model_rms"] = np.sqrt(np.array([np.sum(wp[a:b] * r["dmean"][a:b] ** 2) / np.sum(wp[a:b])
+                                                  for a, b in zip(off[:R], off[1:R + 1])]))
+        out["rms"] = np.sqrt(out["msd"])
+        out["rms_mean"], out["rms_std"] = out["rms"].mean(axis=0), out["rms"].std(axis=0, ddof=1) if M > 1 else np.full(R, np.nan)
+        if len(np.ravel(probs)):
+            out["rms_quantiles"] = np.quantile(out["rms"], np.ravel(probs), axis=0)
+    out["msd_mean"], out["msd_std"] = r["mean"][:R], r["std"][:R]
+    if r["quantiles"] is not None:
+        out["msd_quantiles"] = r["quantiles"][:, :R]
+    if r["hist"] is not None:
+        out["msd_hist"] = r["hist"][:R]
+    if convergence:
+        rhat, ess, lags = r["rhat"][:R], r["ess"][:R], r["lags"][:R]
+        out.update(rhat=rhat, ess=ess, lags=lags)
+        with np.errstate(invalid="ignore"):
+            out["summary"] = {
+                "rhat_max": float(np.nanmax(rhat)) if not np.all(np.isnan(rhat)) else float("nan"),
+                "ess_min": float(np.nanmin(ess)) if not np.all(np.isnan(ess)) else float("nan"),
+                "frac_rhat_above_1_01": float(np.mean(rhat > 1.01)),
+                "frac_capped": float(np.mean(lags < 0)),
+                "nan_columns": int(np.sum(np.isnan(rhat) | np.isnan(ess))),
+                "n": min(lens) // 2, "m": 2 * len(lens)}
+    return out
 
 
 def posterior_predictive(model_hist, dataStruct, TD_parameters, probs=(0.05, 0.5, 0.95), bins=None, convergence=False,
