@@ -209,11 +209,7 @@ int cov_check(td_ctx *ctx, const td_covariance *cv, const char *who) {
 }
 
 hipError_t timed_stats(td_ctx *ctx, const double *values, int nmodels, int n, double *mean, double *sd) {
-    Timer *tm = ctx->timer.on ? &ctx->timer : nullptr;
-    hipEvent_t t0 = tm ? tm->begin(ctx->stream) : nullptr;
-    const hipError_t e = launch_raster_stats(values, nmodels, n, mean, sd, ctx->stream);
-    if (tm) tm->end("raster_stats", t0, ctx->stream);
-    return e;
+    return timed_launch(ctx, "raster_stats", [&] { return launch_raster_stats(values, nmodels, n, mean, sd, ctx->stream); });
 }
 
 // Both entry points; E and cv have been checked (ensemble.h, cov_check).
@@ -230,7 +226,6 @@ int cov_core(td_ctx *ctx, const char *who, const Ensemble &E, const td_covarianc
     VolSearch S;
     if (int rc = volume_build(ctx, who, E, &S)) return rc;
     hipStream_t s = ctx->stream;
-    Timer *tm = ctx->timer.on ? &ctx->timer : nullptr;
     const VolPlan plan = volume_plan(M, nq, kVolDefaultBudget, ctx->vol_slab_nodes);
     const int64_t cap = std::max<int64_t>(std::min(plan.nodes, std::max(nq, nt)), 1), capq = std::min(plan.nodes, nq);
     const int64_t ngroups = (T + G - 1) / G;
@@ -265,10 +260,9 @@ int cov_core(td_ctx *ctx, const char *who, const Ensemble &E, const td_covarianc
     if (nq > 0) {
         const long total = (long)n_Ac;
         const unsigned blocks = (unsigned)std::min<long>((total + 255) / 256, 1L << 20);
-        hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
-        hipLaunchKernelGGL(k_cov_center, dim3(blocks), dim3(256), 0, s, dA, dmt, (int)M, (int)T, total, dAc);
-        if (tm) tm->end("cov_center", t0, s);
-        TD_HIP(ctx, hipGetLastError());
+        TD_HIP(ctx, timed_launch(ctx, "cov_center", [&] {
+                   hipLaunchKernelGGL(k_cov_center, dim3(blocks), dim3(256), 0, s, dA, dmt, (int)M, (int)T, total, dAc);
+               }));
     }
     for (int64_t q0 = 0; q0 < nq; q0 += plan.nodes) {
         const int64_t ns = std::min(plan.nodes, nq - q0);
@@ -280,15 +274,14 @@ int cov_core(td_ctx *ctx, const char *who, const Ensemble &E, const td_covarianc
             TD_HIP(ctx, hipMemcpyAsync(cv->mean_out + q0, dm, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, s));
             TD_HIP(ctx, hipMemcpyAsync(cv->std_out + q0, dsd, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, s));
         }
-        hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
-        for (int64_t g0 = 0; g0 < ngroups; g0 += kCovMaxGroupsY) {
-            const int64_t ng = std::min<int64_t>(kCovMaxGroupsY, ngroups - g0);
-            hipLaunchKernelGGL(k_cov_targets<G>, dim3((unsigned)((ns + kCovThreads - 1) / kCovThreads), (unsigned)ng),
-                               dim3(kCovThreads), lds, s, dv, (int)M, (int)ns, dm, dsd, dAc, dst, (int)T, (int)g0,
-                               want_cov ? dcov : nullptr, want_corr ? dcorr : nullptr);
-        }
-        if (tm) tm->end("cov_targets", t0, s);
-        TD_HIP(ctx, hipGetLastError());
+        TD_HIP(ctx, timed_launch(ctx, "cov_targets", [&] {
+                   for (int64_t g0 = 0; g0 < ngroups; g0 += kCovMaxGroupsY) {
+                       const int64_t ng = std::min<int64_t>(kCovMaxGroupsY, ngroups - g0);
+                       hipLaunchKernelGGL(k_cov_targets<G>, dim3((unsigned)((ns + kCovThreads - 1) / kCovThreads), (unsigned)ng),
+                                          dim3(kCovThreads), lds, s, dv, (int)M, (int)ns, dm, dsd, dAc, dst, (int)T, (int)g0,
+                                          want_cov ? dcov : nullptr, want_corr ? dcorr : nullptr);
+                   }
+               }));
         // the [T][ns] rows go out through the pinned block, as the volume's quantile rows do
         if (want_cov) TD_HIP(ctx, hipMemcpyAsync(hcov, dcov, sizeof(double) * (size_t)T * (size_t)ns, hipMemcpyDeviceToHost, s));
         if (want_corr)
@@ -319,21 +312,16 @@ extern "C" int td_rasterize_covariance(td_ctx *ctx, int64_t nmodels, const int64
                                        const double *yCell, const double *zCell, const double *zeta,
                                        const td_covariance *cov) {
     const char *who = "td_rasterize_covariance";
-    if (int rc = cov_check(ctx, cov, who)) return rc;
-    if (int rc = ensemble_check_arrays(ctx, who, nmodels, cell_off, xCell, yCell, zCell, zeta)) return rc;
-    if (!ctx) return set_err(nullptr, TD_ERR_ARG, std::string(who) + ": ctx is NULL");
-    return cov_core(ctx, who, Ensemble(nmodels, cell_off, xCell, yCell, zCell, zeta), cov);
+    return ensemble_entry_arrays(
+        ctx, who, Ensemble(nmodels, cell_off, xCell, yCell, zCell, zeta), nullptr, [&] { return cov_check(ctx, cov, who); },
+        [&](const Ensemble &E) { return cov_core(ctx, who, E, cov); });
 }
 
 extern "C" int td_history_covariance(td_ctx *ctx, td_history *const *hs, int64_t nh, const td_covariance *cov) {
     const char *who = "td_history_covariance";
-    if (int rc = cov_check(ctx, cov, who)) return rc;
-    Ensemble E;
-    if (int rc = ensemble_from_histories(ctx, who, hs, nh, HistoryRule::SameDevice, &E)) return rc;
-    if (int rc = ensemble_check_device(ctx, who, E)) return rc;  // (of the first history's device without a context)
-    if (!ctx) return set_err(nullptr, TD_ERR_ARG, std::string(who) + ": ctx is NULL");
-    if (int rc = ensemble_sync_foreign(ctx, E)) return rc;
-    return cov_core(ctx, who, E, cov);
+    return ensemble_entry_histories(
+        ctx, who, hs, nh, nullptr, [&] { return cov_check(ctx, cov, who); },
+        [&](const Ensemble &E) { return cov_core(ctx, who, E, cov); });
 }
 
 extern "C" int tdt_covariance_group(void) { return kCovGroup; }

@@ -4,6 +4,7 @@
 
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/tdstar.h"
@@ -124,6 +125,22 @@ int hip_err(td_ctx *ctx, hipError_t e, const char *what);
         hipError_t e_ = (call);                           \
         if (e_ != hipSuccess) return hip_err(ctx, e_, #call); \
     } while (0)
+// What `launch` issues on ctx->stream, between the timer's events under `name` when timing is on.  -> the launch
+// error, for TD_HIP: launch's own when it returns one (launch_raster_stats), else hipGetLastError().
+template <class Launch>
+hipError_t timed_launch(td_ctx *ctx, const char *name, Launch launch) {
+    Timer *tm = ctx->timer.on ? &ctx->timer : nullptr;
+    hipEvent_t t0 = tm ? tm->begin(ctx->stream) : nullptr;
+    if constexpr (std::is_void<decltype(launch())>::value) {
+        launch();
+        if (tm) tm->end(name, t0, ctx->stream);
+        return hipGetLastError();
+    } else {
+        const hipError_t e = launch();
+        if (tm) tm->end(name, t0, ctx->stream);
+        return e;
+    }
+}
 // Room for `bytes` in a grow-only workspace: nothing is allocated when they fit, a buffer never
 // shrinks, and a failed allocation leaves the pointer null and the capacity 0.  td_destroy frees them.
 inline int grow(td_ctx *ctx, DevBuf &b, size_t bytes) {

@@ -1,7 +1,9 @@
-// ensemble.h -- what the posterior entry points (raster.hip, volume.hip, predict.hip, covariance.hip) share on
-// the host: the ensemble of models a call is about, its checks, the fold of histories into one, and the tail
-// of a slab of the value matrix.  Every core function takes a `const Ensemble &` whose every member has been
-// checked by the functions here.
+// ensemble.h -- what the posterior entry points (raster.hip, volume.hip, predict.hip, covariance.hip,
+// interfaces.hip, regions.hip, support.hip, recovery.hip, and region_sums.h for the last three's shared part)
+// share on the host: the ensemble of models a call is about, its checks, the fold of histories into one, the
+// order of an entry point's steps (ensemble_entry_arrays, ensemble_entry_histories), and the tail of a slab of
+// the value matrix.  Every core function takes a `const Ensemble &` whose every member has been checked by the
+// functions here.
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -105,6 +107,38 @@ inline int ensemble_sync_foreign(td_ctx *ctx, const Ensemble &E) {
     for (const td_history *h : *E.segs)
         if (h->ctx != ctx) TD_HIP(ctx, hipStreamSynchronize(h->ctx->stream));
     return TD_OK;
+}
+
+// The td_rasterize_X / td_history_X pair of covariance, interfaces, regions, support and recovery: the steps of
+// an entry point in the order the callers rely on (which refusal comes first is part of the contract).  The array
+// form takes the caller's arrays as an unchecked Ensemble.
+//   check()  the request's own checks, which need no context
+//   conv     the request's convergence part (null: none, or the request itself is NULL): the chains are checked
+//   core(E)  the work, on a checked ensemble and a non-NULL context
+// Three entry points keep an order of their own and do not come through here: td_rasterize_predict and
+// td_history_predict (arrays before chains when models are given, ctx before the device) and td_history_volume
+// (HistoryRule::SameContext).
+template <class Check, class Core>
+int ensemble_entry_arrays(td_ctx *ctx, const char *who, const Ensemble &E, const td_convergence *conv, Check check, Core core) {
+    if (int rc = check()) return rc;
+    if (conv)
+        if (int rc = conv_check_chains(ctx, E.nchains, E.chain_len, E.nmodels, who)) return rc;
+    if (int rc = ensemble_check_arrays(ctx, who, E.nmodels, E.cell_off, E.x, E.y, E.z, E.zeta)) return rc;
+    if (!ctx) return set_err(nullptr, TD_ERR_ARG, std::string(who) + ": ctx is NULL");
+    return core(E);
+}
+template <class Check, class Core>
+int ensemble_entry_histories(td_ctx *ctx, const char *who, td_history *const *hs, int64_t nh, const td_convergence *conv,
+                             Check check, Core core) {
+    if (int rc = check()) return rc;
+    Ensemble E;
+    if (int rc = ensemble_from_histories(ctx, who, hs, nh, HistoryRule::SameDevice, &E)) return rc;
+    if (conv)  // (one history with samples is one chain)
+        if (int rc = conv_check_chains(ctx, E.nchains, E.chain_len, E.nmodels, who)) return rc;
+    if (int rc = ensemble_check_device(ctx, who, E)) return rc;  // (of the first history's device without a context)
+    if (!ctx) return set_err(nullptr, TD_ERR_ARG, std::string(who) + ": ctx is NULL");
+    if (int rc = ensemble_sync_foreign(ctx, E)) return rc;
+    return core(E);
 }
 
 // E.segs: each history's packed samples behind the ones before, component by component, into the SoA block dc

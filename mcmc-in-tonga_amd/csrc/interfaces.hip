@@ -297,7 +297,6 @@ int iface_core(td_ctx *ctx, const char *who, const Ensemble &E, const td_interfa
     VolSearch S;
     if (int rc = volume_build(ctx, who, E, &S)) return rc;
     hipStream_t s = ctx->stream;
-    Timer *tm = ctx->timer.on ? &ctx->timer : nullptr;
     std::vector<int2> leaves;
     if (faces) iface_leaves(0, (int)M - 1, &leaves);
     const int64_t nleaves = (int64_t)leaves.size(), cap = std::min(plan.nodes, nq), cols = sweep ? plan.maxcols : 0;
@@ -335,11 +334,10 @@ int iface_core(td_ctx *ctx, const char *who, const Ensemble &E, const td_interfa
         const int64_t total = E.total();
         if (total > 0) {
             const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 1 << 16);
-            hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
-            hipLaunchKernelGGL(k_iface_density, dim3(blocks), dim3(256), 0, s, S.cells, (long)S.cs, (long)total, dmid, (int)nx,
-                               (int)ny, (int)nz, ddens, ddens + nq);
-            if (tm) tm->end("iface_density", t0, s);
-            TD_HIP(ctx, hipGetLastError());
+            TD_HIP(ctx, timed_launch(ctx, "iface_density", [&] {
+                       hipLaunchKernelGGL(k_iface_density, dim3(blocks), dim3(256), 0, s, S.cells, (long)S.cs, (long)total, dmid,
+                                          (int)nx, (int)ny, (int)nz, ddens, ddens + nq);
+                   }));
         }
         TD_HIP(ctx, hipMemcpyAsync(w->density_out, ddens, sizeof(int64_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
         if (w->skipped_out) TD_HIP(ctx, hipMemcpyAsync(w->skipped_out, ddens + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -364,31 +362,27 @@ int iface_core(td_ctx *ctx, const char *who, const Ensemble &E, const td_interfa
             if (int rc = volume_sweep(ctx, S, 0, M, dq, nc, dv)) return rc;
             if (!S.grid) brute_pairs += M * nc;
             if (stats) {  // k_raster_stats column by column: the owned nodes are the first ns
-                hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
-                const hipError_t e = launch_raster_stats(dv, (int)M, (int)nc, dm, dsd, s);
-                if (tm) tm->end("raster_stats", t0, s);
-                TD_HIP(ctx, e);
+                TD_HIP(ctx, timed_launch(ctx, "raster_stats", [&] { return launch_raster_stats(dv, (int)M, (int)nc, dm, dsd, s); }));
                 TD_HIP(ctx, hipMemcpyAsync(w->mean_out + q0, dm, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, s));
                 TD_HIP(ctx, hipMemcpyAsync(w->std_out + q0, dsd, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, s));
             }
             if (faces) {
                 const unsigned tiles = (unsigned)((ns + kIfaceThreads - 1) / kIfaceThreads), nl = (unsigned)nleaves;
-                hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
-                if (nthr == 0)
-                    launch_faces<0>(s, tiles, nl, dv, sl, (int)nx, (int)ny, (int)nz, dleaf, thr, nthr, dps, dpc);
-                else if (nthr == 1)
-                    launch_faces<1>(s, tiles, nl, dv, sl, (int)nx, (int)ny, (int)nz, dleaf, thr, nthr, dps, dpc);
-                else if (nthr == 2)
-                    launch_faces<2>(s, tiles, nl, dv, sl, (int)nx, (int)ny, (int)nz, dleaf, thr, nthr, dps, dpc);
-                else if (nthr <= 4)
-                    launch_faces<4>(s, tiles, nl, dv, sl, (int)nx, (int)ny, (int)nz, dleaf, thr, nthr, dps, dpc);
-                else
-                    launch_faces<8>(s, tiles, nl, dv, sl, (int)nx, (int)ny, (int)nz, dleaf, thr, nthr, dps, dpc);
-                hipLaunchKernelGGL(k_iface_combine, dim3((unsigned)((ns + 255) / 256)), dim3(256),
-                                   sizeof(double) * 256 * (size_t)cov_levels(M), s, dps, dpc, (int)nleaves,
-                                   (int)M, ncnt, (int)ns, (long)q0, (int)nx, (int)ny, (int)nz, dout);
-                if (tm) tm->end("iface_faces", t0, s);
-                TD_HIP(ctx, hipGetLastError());
+                TD_HIP(ctx, timed_launch(ctx, "iface_faces", [&] {  // (both launches under the one name)
+                           if (nthr == 0)
+                               launch_faces<0>(s, tiles, nl, dv, sl, (int)nx, (int)ny, (int)nz, dleaf, thr, nthr, dps, dpc);
+                           else if (nthr == 1)
+                               launch_faces<1>(s, tiles, nl, dv, sl, (int)nx, (int)ny, (int)nz, dleaf, thr, nthr, dps, dpc);
+                           else if (nthr == 2)
+                               launch_faces<2>(s, tiles, nl, dv, sl, (int)nx, (int)ny, (int)nz, dleaf, thr, nthr, dps, dpc);
+                           else if (nthr <= 4)
+                               launch_faces<4>(s, tiles, nl, dv, sl, (int)nx, (int)ny, (int)nz, dleaf, thr, nthr, dps, dpc);
+                           else
+                               launch_faces<8>(s, tiles, nl, dv, sl, (int)nx, (int)ny, (int)nz, dleaf, thr, nthr, dps, dpc);
+                           hipLaunchKernelGGL(k_iface_combine, dim3((unsigned)((ns + 255) / 256)), dim3(256),
+                                              sizeof(double) * 256 * (size_t)cov_levels(M), s, dps, dpc, (int)nleaves, (int)M, ncnt,
+                                              (int)ns, (long)q0, (int)nx, (int)ny, (int)nz, dout);
+                       }));
                 TD_HIP(ctx, hipMemcpyAsync(hout, dout, sizeof(int64_t) * (size_t)(ncnt + 3) * (size_t)ns, hipMemcpyDeviceToHost, s));
             }
             TD_HIP(ctx, hipStreamSynchronize(s));  // the pinned block is packed again for the next slab
@@ -456,21 +450,16 @@ extern "C" int td_rasterize_interfaces(td_ctx *ctx, int64_t nmodels, const int64
                                        const double *yCell, const double *zCell, const double *zeta,
                                        const td_interfaces *want) {
     const char *who = "td_rasterize_interfaces";
-    if (int rc = iface_check(ctx, want, who)) return rc;
-    if (int rc = ensemble_check_arrays(ctx, who, nmodels, cell_off, xCell, yCell, zCell, zeta)) return rc;
-    if (!ctx) return set_err(nullptr, TD_ERR_ARG, std::string(who) + ": ctx is NULL");
-    return iface_core(ctx, who, Ensemble(nmodels, cell_off, xCell, yCell, zCell, zeta), want);
+    return ensemble_entry_arrays(
+        ctx, who, Ensemble(nmodels, cell_off, xCell, yCell, zCell, zeta), nullptr, [&] { return iface_check(ctx, want, who); },
+        [&](const Ensemble &E) { return iface_core(ctx, who, E, want); });
 }
 
 extern "C" int td_history_interfaces(td_ctx *ctx, td_history *const *hs, int64_t nh, const td_interfaces *want) {
     const char *who = "td_history_interfaces";
-    if (int rc = iface_check(ctx, want, who)) return rc;
-    Ensemble E;
-    if (int rc = ensemble_from_histories(ctx, who, hs, nh, HistoryRule::SameDevice, &E)) return rc;
-    if (int rc = ensemble_check_device(ctx, who, E)) return rc;  // (of the first history's device without a context)
-    if (!ctx) return set_err(nullptr, TD_ERR_ARG, std::string(who) + ": ctx is NULL");
-    if (int rc = ensemble_sync_foreign(ctx, E)) return rc;
-    return iface_core(ctx, who, E, want);
+    return ensemble_entry_histories(
+        ctx, who, hs, nh, nullptr, [&] { return iface_check(ctx, want, who); },
+        [&](const Ensemble &E) { return iface_core(ctx, who, E, want); });
 }
 
 extern "C" int tdt_interfaces_plan(int64_t nmodels, int64_t nx, int64_t ny, int64_t nz, int64_t budget, int64_t forced,

@@ -18,11 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <climits>
-#include <cmath>
-#include <cstring>
 #include <string>
-#include <vector>
 
 #include "../../include/tdstar_regions.h"
 #include "covariance.h"
@@ -42,7 +38,6 @@ struct RegionTerm {  // t[m][p] = w[p] * V[m][p]
 
 constexpr int kRegPairs = 16;         // k_region_greater: 16 x 16 pairs per workgroup
 constexpr int kRegChunk = 1024;       // ... and this many models, 64 at a time through LDS
-constexpr int64_t kRegMaxRegions = kVolMaxSlabNodes;             // the statistics take one slab's columns
 constexpr int64_t kRegMaxCounters = kVolDefaultBudget / 8;       // greater_out: 1 GiB of 64-bit counters
 
 // cnt [R][R], zeroed.  Workgroup (x: chunk of kRegChunk models, y: 16 regions b, z: 16 regions a).
@@ -69,25 +64,13 @@ __global__ __launch_bounds__(256) void k_region_greater(const double *__restrict
     if (count > 0 && ra + i < R && rb + j < R) atomicAdd(&cnt[(ra + i) * R + rb + j], (unsigned long long)count);
 }
 
+RegionList region_list(const td_regions *w) { return {w->px, w->py, w->pz, w->w, w->np, w->reg_off, w->nreg, w->normalize}; }
+
 // the checks of both entry points that need no context and no HIP call, in the header's order
 int regions_check(td_ctx *ctx, const td_regions *w, const char *who) {
     const std::string n(who);
     if (!w) return set_err(ctx, TD_ERR_ARG, n + ": want is NULL");
-    if (w->np < 1 || w->nreg < 1) return set_err(ctx, TD_ERR_ARG, n + ": np and nreg must be >= 1");
-    if (!w->px || !w->py || !w->pz || !w->reg_off) return set_err(ctx, TD_ERR_ARG, n + ": px, py, pz and reg_off must be given");
-    if (w->reg_off[0] != 0) return set_err(ctx, TD_ERR_ARG, n + ": reg_off[0] must be 0");
-    for (int64_t r = 0; r < w->nreg; ++r) {
-        if (w->reg_off[r + 1] < w->reg_off[r]) return set_err(ctx, TD_ERR_ARG, n + ": reg_off is not monotone");
-        if (w->reg_off[r + 1] == w->reg_off[r]) return set_err(ctx, TD_ERR_ARG, n + ": a region without points");
-        if (w->reg_off[r + 1] > w->np) return set_err(ctx, TD_ERR_ARG, n + ": reg_off[nreg] must be np");
-    }
-    if (w->reg_off[w->nreg] != w->np) return set_err(ctx, TD_ERR_ARG, n + ": reg_off[nreg] must be np");
-    const double *vec[4] = {w->px, w->py, w->pz, w->w};
-    const char *name[4] = {"px", "py", "pz", "w"};
-    for (int a = 0; a < 4; ++a)
-        for (int64_t i = 0; vec[a] && i < w->np; ++i)
-            if (!std::isfinite(vec[a][i])) return set_err(ctx, TD_ERR_ARG, n + ": " + name[a] + " is not finite");
-    if (w->normalize != 0 && w->normalize != 1) return set_err(ctx, TD_ERR_ARG, n + ": normalize must be 0 or 1");
+    if (int rc = region_list_check(ctx, who, region_list(w), nullptr)) return rc;
     if (!w->series_out && !w->weight_out && !w->mean_out && !w->std_out && !w->greater_out && !w->marg && !w->conv)
         return set_err(ctx, TD_ERR_ARG, n + ": no output asked for");
     if (!w->mean_out != !w->std_out) return set_err(ctx, TD_ERR_ARG, n + ": mean_out and std_out must be given together");
@@ -100,41 +83,19 @@ int regions_check(td_ctx *ctx, const td_regions *w, const char *who) {
 
 // Both entry points; E and w have been checked (ensemble.h, regions_check).
 int regions_core(td_ctx *ctx, const char *who, const Ensemble &E, const td_regions *w) {
-    const std::string n(who);
     const int64_t M = E.nmodels, np = w->np, R = w->nreg;
-    if (R > kRegMaxRegions) return set_err(ctx, TD_ERR_ARG, n + ": more than 2^18 regions");
-    if (M > kVolDefaultBudget / 8 / R)
-        return set_err(ctx, TD_ERR_ARG, n + ": the series [nmodels][nreg] exceed 1 GiB");
+    const RegionList list = region_list(w);
+    RegionPlan P;
+    if (int rc = region_limits(ctx, who, M, R)) return rc;
     if (w->greater_out && R * R > kRegMaxCounters)
-        return set_err(ctx, TD_ERR_ARG, n + ": greater_out of more than 2^27 counters (1 GiB)");
-    // the leaves of all regions behind one another: leaf l = the points [leafp[l], leafp[l + 1])
-    std::vector<long long> leafp, regleaf((size_t)R + 1);
-    std::vector<double> W((size_t)R);
-    int64_t most = 1;
-    for (int64_t r = 0; r < R; ++r) {
-        const int64_t lo = w->reg_off[r], cnt = w->reg_off[r + 1] - lo;
-        regleaf[(size_t)r] = (long long)leafp.size();
-        region_leaves(lo, 0, cnt - 1, &leafp);
-        W[(size_t)r] = region_weight(w->w ? w->w + lo : nullptr, 0, cnt - 1);
-        most = std::max(most, cnt);
-    }
-    const int64_t L = (int64_t)leafp.size();
-    regleaf[(size_t)R] = L;
-    leafp.push_back(np);
-    if (M > kVolDefaultBudget / 8 / L)
-        return set_err(ctx, TD_ERR_ARG, n + ": the leaf sums [leaves][nmodels] exceed 1 GiB");
-    if (int rc = marg_check_models(ctx, w->marg, M)) return rc;  // (before anything is issued)
-    const VolPlan plan = volume_plan(M, np, kVolDefaultBudget, ctx->vol_slab_nodes);
-    const int64_t cap = std::min(plan.nodes, np);
-    const int mgroups = (int)((M + kRegTile - 1) / kRegTile), mblocks = (int)((M + 255) / 256);
-    if ((cap + 1) * (int64_t)mgroups > INT32_MAX || R * (int64_t)mblocks > INT32_MAX)
-        return set_err(ctx, TD_ERR_ARG, n + ": too many models for one launch");
+        return set_err(ctx, TD_ERR_ARG, std::string(who) + ": greater_out of more than 2^27 counters (1 GiB)");
+    if (int rc = region_plan(ctx, who, M, list, w->marg, &P)) return rc;
+    const int64_t cap = P.cap, L = P.L;
     TD_HIP(ctx, hipSetDevice(ctx->device));
     servers_quiesce(nullptr);
     VolSearch S;
     if (int rc = volume_build(ctx, who, E, &S)) return rc;
     hipStream_t s = ctx->stream;
-    Timer *tm = ctx->timer.on ? &ctx->timer : nullptr;
     // ctx->raster (8-byte words): queries [3][cap] | weights [cap] | V_slab [M][cap] | mean, std [R] | leaf sums
     // [L][M] | F [M][R] | W [R] | counters [R][R] | leafp [L + 1] | regleaf [R + 1]; pinned: queries | weights
     const size_t n_q = 3 * (size_t)cap, n_w = (size_t)cap, n_v = (size_t)M * (size_t)cap, n_ms = 2 * (size_t)R,
@@ -147,56 +108,29 @@ int regions_core(td_ctx *ctx, const char *who, const Ensemble &E, const td_regio
     long long *dlp = reinterpret_cast<long long *>(dW + n_W + n_cnt), *drl = dlp + n_lp;
     double *hw = ctx->h_raster.as<double>() + n_q;
     TD_HIP(ctx, hipStreamSynchronize(s));  // (the pinned block and the workspace are free)
-    TD_HIP(ctx, hipMemcpyAsync(dlp, leafp.data(), sizeof(long long) * n_lp, hipMemcpyHostToDevice, s));
-    TD_HIP(ctx, hipMemcpyAsync(drl, regleaf.data(), sizeof(long long) * n_rl, hipMemcpyHostToDevice, s));
-    TD_HIP(ctx, hipMemcpyAsync(dW, W.data(), sizeof(double) * n_W, hipMemcpyHostToDevice, s));
-    int64_t brute_pairs = 0, la = 0;  // la: the first leaf with a point in the slab
-    for (int64_t c0 = 0; c0 < np; c0 += plan.nodes) {
-        const int64_t ns = std::min(plan.nodes, np - c0);
+    if (int rc = region_upload(ctx, P, dlp, drl, dW)) return rc;
+    int64_t brute_pairs = 0, la = 0;
+    for (int64_t c0 = 0; c0 < np; c0 += P.vol.nodes) {
+        const int64_t ns = std::min(P.vol.nodes, np - c0);
         if (int rc = stage_queries(ctx, w->px, w->py, w->pz, c0, ns, dq)) return rc;
-        if (w->w) {
-            std::memcpy(hw, w->w + c0, sizeof(double) * (size_t)ns);
-            TD_HIP(ctx, hipMemcpyAsync(dw, hw, sizeof(double) * (size_t)ns, hipMemcpyHostToDevice, s));
-        }
+        if (int rc = region_stage_weights(ctx, list, c0, ns, hw, dw)) return rc;
         if (int rc = volume_sweep(ctx, S, 0, M, dq, ns, dv)) return rc;
         if (!S.grid) brute_pairs += M * ns;
-        while (leafp[(size_t)la + 1] <= c0) ++la;
-        int64_t lb = la;  // the last leaf with a point in the slab
-        while (leafp[(size_t)lb + 1] < c0 + ns) ++lb;
-        hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
-        hipLaunchKernelGGL(k_region_sums<RegionTerm>, dim3((unsigned)((lb - la + 1) * mgroups)), dim3(kRegTile), 0, s, dv, (long)ns, (int)M,
-                           (long)c0, dlp, (long)la, mgroups, w->w ? dw : nullptr, dacc);
-        if (tm) tm->end("region_sums", t0, s);
-        TD_HIP(ctx, hipGetLastError());
+        if (int rc = region_sums_slab<RegionTerm>(ctx, "region_sums", P, c0, ns, dv, w->w ? dw : nullptr, dlp, dacc, &la)) return rc;
         TD_HIP(ctx, hipStreamSynchronize(s));  // the pinned block is packed again for the next slab
     }
-    {
-        hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
-        hipLaunchKernelGGL(k_region_combine, dim3((unsigned)(R * mblocks)), dim3(256), sizeof(double) * 256 * (size_t)cov_levels(most),
-                           s, dacc, (int)M, mblocks, drl, dlp, dW, (int)w->normalize, (long)R, dF);
-        if (tm) tm->end("region_combine", t0, s);
-        TD_HIP(ctx, hipGetLastError());
-    }
+    if (int rc = region_combine(ctx, "region_combine", P, dacc, drl, dlp, dW, (int)w->normalize, dF)) return rc;
     if (w->greater_out) {
         TD_HIP(ctx, hipMemsetAsync(dcnt, 0, sizeof(unsigned long long) * n_cnt, s));
         const unsigned tiles = (unsigned)((R + kRegPairs - 1) / kRegPairs);
-        hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
-        hipLaunchKernelGGL(k_region_greater, dim3((unsigned)((M + kRegChunk - 1) / kRegChunk), tiles, tiles), dim3(256), 0, s, dF,
-                           (int)M, (long)R, dcnt);
-        if (tm) tm->end("region_greater", t0, s);
-        TD_HIP(ctx, hipGetLastError());
+        TD_HIP(ctx, timed_launch(ctx, "region_greater", [&] {
+                   hipLaunchKernelGGL(k_region_greater, dim3((unsigned)((M + kRegChunk - 1) / kRegChunk), tiles, tiles), dim3(256), 0,
+                                      s, dF, (int)M, (long)R, dcnt);
+               }));
         TD_HIP(ctx, hipMemcpyAsync(w->greater_out, dcnt, sizeof(int64_t) * n_cnt, hipMemcpyDeviceToHost, s));
     }
-    {  // the regions in the place of a slab's columns: the slab is the whole matrix
-        const SlabWant want{R, w->mean_out, w->std_out, w->series_out, w->marg, w->conv};
-        hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
-        const int rc = slab_statistics(ctx, E, want, dF, 0, R, dm, dsd, false, nullptr);
-        if (tm) tm->end("raster_stats", t0, s);
-        if (rc) return rc;
-    }
-    TD_HIP(ctx, hipStreamSynchronize(s));
-    if (w->weight_out) std::memcpy(w->weight_out, W.data(), sizeof(double) * n_W);
-    return volume_counters_finish(ctx, S, brute_pairs);  // (tdt_volume_counters: this call's sweeps)
+    if (int rc = region_tail(ctx, E, SlabWant{R, w->mean_out, w->std_out, w->series_out, w->marg, w->conv}, dF, dm, dsd)) return rc;
+    return region_finish(ctx, P, S, brute_pairs, w->weight_out);
 }
 
 }  // namespace
@@ -209,25 +143,16 @@ extern "C" int td_rasterize_regions(td_ctx *ctx, int64_t nmodels, const int64_t 
                                     const double *yCell, const double *zCell, const double *zeta, int64_t nchains,
                                     const int64_t *chain_len, const td_regions *want) {
     const char *who = "td_rasterize_regions";
-    if (int rc = regions_check(ctx, want, who)) return rc;
-    if (want->conv)
-        if (int rc = conv_check_chains(ctx, nchains, chain_len, nmodels, who)) return rc;
-    if (int rc = ensemble_check_arrays(ctx, who, nmodels, cell_off, xCell, yCell, zCell, zeta)) return rc;
-    if (!ctx) return set_err(nullptr, TD_ERR_ARG, std::string(who) + ": ctx is NULL");
-    return regions_core(ctx, who, Ensemble(nmodels, cell_off, xCell, yCell, zCell, zeta, nchains, chain_len), want);
+    return ensemble_entry_arrays(
+        ctx, who, Ensemble(nmodels, cell_off, xCell, yCell, zCell, zeta, nchains, chain_len), want ? want->conv : nullptr,
+        [&] { return regions_check(ctx, want, who); }, [&](const Ensemble &E) { return regions_core(ctx, who, E, want); });
 }
 
 extern "C" int td_history_regions(td_ctx *ctx, td_history *const *hs, int64_t nh, const td_regions *want) {
     const char *who = "td_history_regions";
-    if (int rc = regions_check(ctx, want, who)) return rc;
-    Ensemble E;
-    if (int rc = ensemble_from_histories(ctx, who, hs, nh, HistoryRule::SameDevice, &E)) return rc;
-    if (want->conv)  // (one history with samples is one chain)
-        if (int rc = conv_check_chains(ctx, E.nchains, E.chain_len, E.nmodels, who)) return rc;
-    if (int rc = ensemble_check_device(ctx, who, E)) return rc;  // (of the first history's device without a context)
-    if (!ctx) return set_err(nullptr, TD_ERR_ARG, std::string(who) + ": ctx is NULL");
-    if (int rc = ensemble_sync_foreign(ctx, E)) return rc;
-    return regions_core(ctx, who, E, want);
+    return ensemble_entry_histories(
+        ctx, who, hs, nh, want ? want->conv : nullptr, [&] { return regions_check(ctx, want, who); },
+        [&](const Ensemble &E) { return regions_core(ctx, who, E, want); });
 }
 
 extern "C" int tdt_regions_plan(int64_t nmodels, int64_t np, int64_t budget, int64_t forced, int64_t out[2]) {

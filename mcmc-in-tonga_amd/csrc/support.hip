@@ -238,7 +238,6 @@ int support_core(td_ctx *ctx, const char *who, const Ensemble &E, const td_suppo
     VolSearch S;
     if (int rc = volume_build(ctx, who, E, &S)) return rc;
     hipStream_t s = ctx->stream;
-    Timer *tm = ctx->timer.on ? &ctx->timer : nullptr;
     const VolPlan pp = volume_plan(M, P, kVolDefaultBudget, ctx->vol_slab_nodes);
     const VolPlan qp = volume_plan(M, nq, kVolDefaultBudget, ctx->vol_slab_nodes);
     const int64_t capp = std::min(pp.nodes, P), capq = std::min(qp.nodes, nq), cap = std::max<int64_t>(std::max(capp, capq), 1);
@@ -263,12 +262,8 @@ int support_core(td_ctx *ctx, const char *who, const Ensemble &E, const td_suppo
     if (n_thr) TD_HIP(ctx, hipMemcpyAsync(dthr, w->thr, sizeof(double) * n_thr, hipMemcpyHostToDevice, s));
     if (total > 0) TD_HIP(ctx, hipMemsetAsync(dK, 0, sizeof(long long) * (n_K + n_C), s));
     TD_HIP(ctx, hipMemsetAsync(dorph, 0, sizeof(long long) * (size_t)M, s));
-    {
-        hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
-        hipLaunchKernelGGL(k_sup_index, dim3((unsigned)M), dim3(kSupThreads), 0, s, S.off, comp3);
-        if (tm) tm->end("sup_index", t0, s);
-        TD_HIP(ctx, hipGetLastError());
-    }
+    TD_HIP(ctx, timed_launch(ctx, "sup_index",
+                             [&] { hipLaunchKernelGGL(k_sup_index, dim3((unsigned)M), dim3(kSupThreads), 0, s, S.off, comp3); }));
     int64_t brute_pairs = 0;
     const auto &g = ctx->g;
     for (int64_t p0 = 0; p0 < P; p0 += pp.nodes) {  // who owns the ray points
@@ -278,20 +273,16 @@ int support_core(td_ctx *ctx, const char *who, const Ensemble &E, const td_suppo
             TD_HIP(ctx, hipMemcpyAsync(dq + d * ns, src[d] + p0, sizeof(double) * (size_t)ns, hipMemcpyDeviceToDevice, s));
         if (int rc = volume_sweep(ctx, S, 0, M, dq, ns, dv)) return rc;
         if (!S.grid) brute_pairs += M * ns;
-        hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
-        hipLaunchKernelGGL(k_sup_scatter, dim3((unsigned)M), dim3(kSupThreads), 12 * (size_t)lds_cells, s, dv, (int)ns, S.off,
-                           n_k ? dk + p0 : nullptr, lds_cells, reinterpret_cast<unsigned long long *>(dK), dC,
-                           reinterpret_cast<unsigned long long *>(dorph));
-        if (tm) tm->end("sup_scatter", t0, s);
-        TD_HIP(ctx, hipGetLastError());
+        TD_HIP(ctx, timed_launch(ctx, "sup_scatter", [&] {
+                   hipLaunchKernelGGL(k_sup_scatter, dim3((unsigned)M), dim3(kSupThreads), 12 * (size_t)lds_cells, s, dv, (int)ns, S.off,
+                                      n_k ? dk + p0 : nullptr, lds_cells, reinterpret_cast<unsigned long long *>(dK), dC,
+                                      reinterpret_cast<unsigned long long *>(dorph));
+               }));
     }
-    {
-        hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
-        hipLaunchKernelGGL(k_sup_finish, dim3((unsigned)M), dim3(kSupThreads), 0, s, S.off, dK, dC, e, comp3,
-                           w->count_out ? dc64 : nullptr, dbar);
-        if (tm) tm->end("sup_finish", t0, s);
-        TD_HIP(ctx, hipGetLastError());
-    }
+    TD_HIP(ctx, timed_launch(ctx, "sup_finish", [&] {
+               hipLaunchKernelGGL(k_sup_finish, dim3((unsigned)M), dim3(kSupThreads), 0, s, S.off, dK, dC, e, comp3,
+                                  w->count_out ? dc64 : nullptr, dbar);
+           }));
     if (w->cell_out && total > 0)
         TD_HIP(ctx, hipMemcpyAsync(w->cell_out, comp3, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, s));
     if (w->count_out && total > 0)
@@ -307,11 +298,10 @@ int support_core(td_ctx *ctx, const char *who, const Ensemble &E, const td_suppo
         if (!S.grid) brute_pairs += M * ns;
         if (nthr > 0) {
             const unsigned groups = (unsigned)std::min<int64_t>((nthr + kSupThr - 1) / kSupThr, 65535);
-            hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
-            hipLaunchKernelGGL(k_sup_exceed, dim3((unsigned)((ns + kSupThreads - 1) / kSupThreads), groups), dim3(kSupThreads), 0, s,
-                               dv, (int)M, (int)ns, dthr, (int)nthr, dex);
-            if (tm) tm->end("sup_exceed", t0, s);
-            TD_HIP(ctx, hipGetLastError());
+            TD_HIP(ctx, timed_launch(ctx, "sup_exceed", [&] {
+                       hipLaunchKernelGGL(k_sup_exceed, dim3((unsigned)((ns + kSupThreads - 1) / kSupThreads), groups),
+                                          dim3(kSupThreads), 0, s, dv, (int)M, (int)ns, dthr, (int)nthr, dex);
+                   }));
             TD_HIP(ctx, hipMemcpy2DAsync(w->exceed_out + q0, sizeof(int64_t) * (size_t)nq, dex, sizeof(int64_t) * (size_t)ns,
                                          sizeof(int64_t) * (size_t)ns, (size_t)nthr, hipMemcpyDeviceToHost, s));
         }
@@ -334,28 +324,20 @@ extern "C" int td_rasterize_support(td_ctx *ctx, int64_t nmodels, const int64_t 
     const char *who = "td_rasterize_support";
     std::vector<long long> kq;
     int e = 0;
-    if (int rc = support_check(ctx, want, who, &kq, &e)) return rc;
-    if (want->conv)
-        if (int rc = conv_check_chains(ctx, nchains, chain_len, nmodels, who)) return rc;
     // (zeta is no input: the x array stands in its place, and k_sup_index overwrites the copy)
-    if (int rc = ensemble_check_arrays(ctx, who, nmodels, cell_off, xCell, yCell, zCell, xCell)) return rc;
-    if (!ctx) return set_err(nullptr, TD_ERR_ARG, std::string(who) + ": ctx is NULL");
-    return support_core(ctx, who, Ensemble(nmodels, cell_off, xCell, yCell, zCell, xCell, nchains, chain_len), want, kq, e);
+    return ensemble_entry_arrays(
+        ctx, who, Ensemble(nmodels, cell_off, xCell, yCell, zCell, xCell, nchains, chain_len), want ? want->conv : nullptr,
+        [&] { return support_check(ctx, want, who, &kq, &e); },
+        [&](const Ensemble &E) { return support_core(ctx, who, E, want, kq, e); });
 }
 
 extern "C" int td_history_support(td_ctx *ctx, td_history *const *hs, int64_t nh, const td_support *want) {
     const char *who = "td_history_support";
     std::vector<long long> kq;
     int e = 0;
-    if (int rc = support_check(ctx, want, who, &kq, &e)) return rc;
-    Ensemble E;
-    if (int rc = ensemble_from_histories(ctx, who, hs, nh, HistoryRule::SameDevice, &E)) return rc;
-    if (want->conv)  // (one history with samples is one chain)
-        if (int rc = conv_check_chains(ctx, E.nchains, E.chain_len, E.nmodels, who)) return rc;
-    if (int rc = ensemble_check_device(ctx, who, E)) return rc;  // (of the first history's device without a context)
-    if (!ctx) return set_err(nullptr, TD_ERR_ARG, std::string(who) + ": ctx is NULL");
-    if (int rc = ensemble_sync_foreign(ctx, E)) return rc;
-    return support_core(ctx, who, E, want, kq, e);
+    return ensemble_entry_histories(
+        ctx, who, hs, nh, want ? want->conv : nullptr, [&] { return support_check(ctx, want, who, &kq, &e); },
+        [&](const Ensemble &E) { return support_core(ctx, who, E, want, kq, e); });
 }
 
 extern "C" int64_t tdt_support_lds_cells(void) { return kSupLdsCells; }

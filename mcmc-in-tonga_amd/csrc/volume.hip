@@ -284,7 +284,6 @@ int volume_build(td_ctx *ctx, const char *who, const Ensemble &E, VolSearch *out
     TD_HIP(ctx, hipSetDevice(ctx->device));
     servers_quiesce(nullptr);  // (both volume entry points; the predictive and covariance calls have stopped them already)
     hipStream_t s = ctx->stream;
-    Timer *tm = ctx->timer.on ? &ctx->timer : nullptr;
     const bool grid = ctx->vol_method == 1 || (ctx->vol_method == 0 && total / nmodels >= kVolGridMinMeanCells);
     // the models: cells SoA | offsets | boxes | grids | bucket prefix | counters
     const size_t b_cells = up256(sizeof(double) * 4 * (size_t)cs), b_off = up256(sizeof(int64_t) * (size_t)(nmodels + 1)),
@@ -313,10 +312,9 @@ int volume_build(td_ctx *ctx, const char *who, const Ensemble &E, VolSearch *out
     std::vector<CellGrid> &grids = out->grids_host;  // (the sources of asynchronous copies: they live as long as the sweeps)
     std::vector<int64_t> &boff = out->boff_host;
     if (grid) {
-        hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
-        hipLaunchKernelGGL(k_vol_boxes, dim3((unsigned)nmodels), dim3(kVolThreads), 0, s, doff, dc, cs, dbox);
-        if (tm) tm->end("vol_boxes", t0, s);
-        TD_HIP(ctx, hipGetLastError());
+        TD_HIP(ctx, timed_launch(ctx, "vol_boxes", [&] {
+                   hipLaunchKernelGGL(k_vol_boxes, dim3((unsigned)nmodels), dim3(kVolThreads), 0, s, doff, dc, cs, dbox);
+               }));
         boxes.resize(6 * (size_t)nmodels);
         TD_HIP(ctx, hipMemcpyAsync(boxes.data(), dbox, sizeof(double) * boxes.size(), hipMemcpyDeviceToHost, s));
         TD_HIP(ctx, hipStreamSynchronize(s));
@@ -339,11 +337,10 @@ int volume_build(td_ctx *ctx, const char *who, const Ensemble &E, VolSearch *out
         dent = reinterpret_cast<BucketEntry *>(gb + 2 * b_start);
         TD_HIP(ctx, hipMemcpyAsync(dgrid, grids.data(), sizeof(CellGrid) * (size_t)nmodels, hipMemcpyHostToDevice, s));
         TD_HIP(ctx, hipMemcpyAsync(dboff, boff.data(), sizeof(int64_t) * (size_t)(nmodels + 1), hipMemcpyHostToDevice, s));
-        t0 = tm ? tm->begin(s) : nullptr;
-        hipLaunchKernelGGL(k_vol_grid_build, dim3((unsigned)nmodels), dim3(kVolThreads), 0, s, doff, dc, cs, dgrid, dboff,
-                           dstart, dcur, dent);
-        if (tm) tm->end("vol_grid_build", t0, s);
-        TD_HIP(ctx, hipGetLastError());
+        TD_HIP(ctx, timed_launch(ctx, "vol_grid_build", [&] {
+                   hipLaunchKernelGGL(k_vol_grid_build, dim3((unsigned)nmodels), dim3(kVolThreads), 0, s, doff, dc, cs, dgrid, dboff,
+                                      dstart, dcur, dent);
+               }));
     }
     out->nmodels = nmodels;
     out->cs = cs;
@@ -365,15 +362,16 @@ int volume_sweep(td_ctx *ctx, const VolSearch &S, int64_t m0, int64_t nm, const 
     if (S.grid) {
         const int nchunks = (int)((ns + kVolThreads - 1) / kVolThreads);
         const int64_t blocks = (int64_t)kVolXcds * ((nm + kVolXcds - 1) / kVolXcds) * nchunks;
-        hipEvent_t t0 = tm ? tm->begin(s) : nullptr;
-        if (ctx->vol_counting)
-            hipLaunchKernelGGL(k_vol_search<true>, dim3((unsigned)blocks), dim3(kVolThreads), 0, s, S.off + m0, S.cells, S.cs,
-                               S.grids + m0, S.boff + m0, S.start, S.ent, q, (int)ns, (int)nm, nchunks, values, S.counters);
-        else
-            hipLaunchKernelGGL(k_vol_search<false>, dim3((unsigned)blocks), dim3(kVolThreads), 0, s, S.off + m0, S.cells, S.cs,
-                               S.grids + m0, S.boff + m0, S.start, S.ent, q, (int)ns, (int)nm, nchunks, values, S.counters);
-        if (tm) tm->end("vol_search", t0, s);
-        TD_HIP(ctx, hipGetLastError());
+        TD_HIP(ctx, timed_launch(ctx, "vol_search", [&] {
+                   if (ctx->vol_counting)
+                       hipLaunchKernelGGL(k_vol_search<true>, dim3((unsigned)blocks), dim3(kVolThreads), 0, s, S.off + m0, S.cells,
+                                          S.cs, S.grids + m0, S.boff + m0, S.start, S.ent, q, (int)ns, (int)nm, nchunks, values,
+                                          S.counters);
+                   else
+                       hipLaunchKernelGGL(k_vol_search<false>, dim3((unsigned)blocks), dim3(kVolThreads), 0, s, S.off + m0, S.cells,
+                                          S.cs, S.grids + m0, S.boff + m0, S.start, S.ent, q, (int)ns, (int)nm, nchunks, values,
+                                          S.counters);
+               }));
     } else {
         TD_HIP(ctx, launch_raster_brute(S.off + m0, S.cells, S.cs, q, (int)ns, (int)nm, values, s, tm));
     }

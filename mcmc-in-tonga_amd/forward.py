@@ -21,6 +21,29 @@ from . import _lib
 from ._lib import check, f64, lib, ptr
 
 
+def _pack_models(models, ncomp=4, empty_ok=True):
+    """(cell offsets [nmodels + 1], the first ``ncomp`` arrays of every model behind one another).  Of no model:
+    empty arrays where ``empty_ok`` (the library refuses the call), else the ValueError of the concatenation."""
+    off = np.zeros(len(models) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(m[0]) for m in models])
+    cat = [f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) if len(models) or not empty_ok
+           else np.zeros(0) for k in range(ncomp)]
+    return off, cat
+
+
+def _chain_lens(chain_len):
+    """The rows of each chain as the int64 array the library reads, or None."""
+    return np.ascontiguousarray(chain_len, dtype=np.int64).ravel() if chain_len is not None else None
+
+
+def _history_handles(histories, count=True):
+    """(the td_history handles of chain.History objects as a C array, the samples they hold -- one library call per
+    history -- or None unless ``count``)"""
+    histories = list(histories)
+    hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
+    return hs, sum(len(h) for h in histories) if count else None
+
+
 class TdContext:
     """A td_ctx: the device-resident copy of a DataStruct's ray geometry."""
 
@@ -132,9 +155,7 @@ class TdContext:
     def rasterize(self, models, qx, qy, qz, want_values=False):
         """td_rasterize: -> (mean[nq], std[nq], values[nmodels, nq] or None).
         models: list of (x, y, z, zeta) cell arrays in model_hist order."""
-        off = np.zeros(len(models) + 1, dtype=np.int64)
-        off[1:] = np.cumsum([len(m[0]) for m in models])
-        cat = [f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) for k in range(4)]
+        off, cat = _pack_models(models, empty_ok=False)
         qx, qy, qz = (f64(np.ravel(a)) for a in (qx, qy, qz))
         nq = len(qx)
         mean, std = np.empty(nq), np.empty(nq)
@@ -146,14 +167,12 @@ class TdContext:
     def rasterize_history(self, histories, qx, qy, qz, want_values=False):
         """td_history_rasterize: ``rasterize`` on the samples of the histories (chain.History), history
         by history in sample order, without the models visiting the host."""
-        histories = list(histories)
-        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
-        nm = sum(len(h) for h in histories)
+        hs, nm = _history_handles(histories)
         qx, qy, qz = (f64(np.ravel(a)) for a in (qx, qy, qz))
         nq = len(qx)
         mean, std = np.empty(nq), np.empty(nq)
         vals = np.empty((nm, nq)) if want_values else None
-        check(lib().td_history_rasterize(self.h, hs, len(histories), ptr(qx), ptr(qy), ptr(qz), nq, ptr(mean),
+        check(lib().td_history_rasterize(self.h, hs, len(hs), ptr(qx), ptr(qy), ptr(qz), nq, ptr(mean),
                                          ptr(std), ptr(vals) if want_values else None), self.h)
         return mean, std, vals
 
@@ -186,9 +205,7 @@ class TdContext:
         hist[nq, nbins + 3] or None).  ``probs``: probabilities in [0, 1] (Julia's default quantile
         over the models at each point); ``bins`` = (nbins, lo, hi): per-point counts below lo, in the
         nbins equal bins of [lo, hi), at or above hi, and NaN.  models as for ``rasterize``."""
-        off = np.zeros(len(models) + 1, dtype=np.int64)
-        off[1:] = np.cumsum([len(m[0]) for m in models])
-        cx, cy, cz, cv = (f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) for k in range(4))
+        off, (cx, cy, cz, cv) = _pack_models(models, empty_ok=False)
         qx, qy, qz = (f64(np.ravel(a)) for a in (qx, qy, qz))
         nq = len(qx)
         mean, std = np.empty(nq), np.empty(nq)
@@ -202,13 +219,12 @@ class TdContext:
     def marginals_history(self, histories, qx, qy, qz, probs=(), bins=None):
         """td_history_marginals: ``marginals`` on the samples of the histories (chain.History), history by
         history in sample order, without the models visiting the host."""
-        histories = list(histories)
-        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
+        hs, _ = _history_handles(histories, count=False)
         qx, qy, qz = (f64(np.ravel(a)) for a in (qx, qy, qz))
         nq = len(qx)
         mean, std = np.empty(nq), np.empty(nq)
         want, held, quant, hist = self._marginals_want(nq, probs, bins)
-        check(lib().td_history_marginals(self.h, hs, len(histories), ptr(qx), ptr(qy), ptr(qz), nq, ptr(mean),
+        check(lib().td_history_marginals(self.h, hs, len(hs), ptr(qx), ptr(qy), ptr(qz), nq, ptr(mean),
                                          ptr(std), ctypes.byref(want)), self.h)
         del held
         return dict(mean=mean, std=std, quantiles=quant, hist=hist)
@@ -216,13 +232,11 @@ class TdContext:
     def zeta_hist(self, histories, bins):
         """td_history_zeta_hist: -> dict(zeta_hist[nbins + 3], ncells[samples]) over every sample of the
         histories; ``bins`` = (nbins, lo, hi), slots as in ``marginals``."""
-        histories = list(histories)
-        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
         nbins, lo, hi = int(bins[0]), float(bins[1]), float(bins[2])
         hist = np.zeros(max(nbins, 0) + 3, dtype=np.int64)
-        nm = sum(len(h) for h in histories)
+        hs, nm = _history_handles(histories)
         ncells = np.zeros(max(nm, 1), dtype=np.int64)
-        check(lib().td_history_zeta_hist(self.h, hs, len(histories), nbins, lo, hi, ptr(hist, _lib._pi64),
+        check(lib().td_history_zeta_hist(self.h, hs, len(hs), nbins, lo, hi, ptr(hist, _lib._pi64),
                                          ptr(ncells, _lib._pi64)), self.h)
         return dict(zeta_hist=hist, ncells=ncells[:nm])
 
@@ -250,6 +264,20 @@ class TdContext:
                                ptr(out.get("lags"), _lib._pi32))
         return w, out
 
+    def _stat_wants(self, ncol, probs, bins, conv, max_lag):
+        """The marginals and convergence parts of a request on ``ncol`` columns -> (address of the td_marginals or
+        None, address of the td_convergence or None, the result entries: quantiles, hist and with ``conv`` rhat, ess,
+        lags; what the addresses point into: keep it until the call has returned)."""
+        entries = dict(quantiles=None, hist=None)
+        marg = cw = arrays = None
+        if len(np.ravel(probs)) or bins is not None:
+            marg, arrays, entries["quantiles"], entries["hist"] = self._marginals_want(ncol, probs, bins)
+        if conv:
+            cw, out = self._convergence_want(ncol, max_lag, self.CONV_ALL)
+            entries.update(out)
+        return (ctypes.addressof(marg) if marg is not None else None, ctypes.addressof(cw) if cw is not None else None,
+                entries, (marg, cw, arrays))
+
     def convergence(self, values, chain_len, max_lag=0, want=CONV_ALL):
         """td_convergence_values: -> dict(rhat[ncol], ess[ncol], lags[ncol]) of the columns of
         ``values`` [M, ncol] (or [M]: one column), whose rows are the chains' samples, chain after chain
@@ -269,9 +297,7 @@ class TdContext:
     def convergence_models(self, models, chain_len, qx, qy, qz, max_lag=0, want=CONV_ALL):
         """td_rasterize_convergence: ``convergence`` of the value matrix of ``rasterize`` (models as
         there, chain after chain), which stays on the device; also ``mean`` and ``std``."""
-        off = np.zeros(len(models) + 1, dtype=np.int64)
-        off[1:] = np.cumsum([len(m[0]) for m in models])
-        cat = [f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) for k in range(4)]
+        off, cat = _pack_models(models, empty_ok=False)
         qx, qy, qz = (f64(np.ravel(a)) for a in (qx, qy, qz))
         nq = len(qx)
         lens = np.ascontiguousarray(chain_len, dtype=np.int64).ravel()
@@ -285,13 +311,12 @@ class TdContext:
     def convergence_history(self, histories, qx, qy, qz, max_lag=0, want=CONV_ALL):
         """td_history_convergence: ``convergence_models`` on the samples of the histories
         (chain.History) where they lie: one history is one chain (one without samples is skipped)."""
-        histories = list(histories)
-        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
+        hs, _ = _history_handles(histories, count=False)
         qx, qy, qz = (f64(np.ravel(a)) for a in (qx, qy, qz))
         nq = len(qx)
         mean, std = np.empty(nq), np.empty(nq)
         w, out = self._convergence_want(nq, max_lag, want)
-        check(lib().td_history_convergence(self.h, hs, len(histories), ptr(qx), ptr(qy), ptr(qz), nq, ptr(mean),
+        check(lib().td_history_convergence(self.h, hs, len(hs), ptr(qx), ptr(qy), ptr(qz), nq, ptr(mean),
                                            ptr(std), ctypes.byref(w)), self.h)
         return dict(out, mean=mean, std=std)
 
@@ -334,17 +359,9 @@ class TdContext:
         mean, std = np.empty(nq), np.empty(nq)
         vals = np.empty((nmodels, nq)) if want_values else None
         out = dict(mean=mean, std=std, values=vals, quantiles=None, hist=None)
-        held = []
-        marg = cw = None
-        if len(np.ravel(probs)) or bins is not None:
-            marg, arrays, out["quantiles"], out["hist"] = self._marginals_want(nq, probs, bins)
-            held.append(arrays)
-        if conv:
-            cw, arrays = self._convergence_want(nq, max_lag, self.CONV_ALL)
-            out.update(arrays)
-        vol = _lib.TdVolume(ptr(qx), ptr(qy), ptr(qz), nq, ptr(mean), ptr(std), ptr(vals),
-                            ctypes.addressof(marg) if marg is not None else None,
-                            ctypes.addressof(cw) if cw is not None else None)
+        marg, cw, entries, held = self._stat_wants(nq, probs, bins, conv, max_lag)
+        out.update(entries)
+        vol = _lib.TdVolume(ptr(qx), ptr(qy), ptr(qz), nq, ptr(mean), ptr(std), ptr(vals), marg, cw)
         call(ctypes.byref(vol))
         del held
         return out
@@ -355,10 +372,8 @@ class TdContext:
         slab by slab.  -> dict(mean[nq], std[nq], values[nmodels, nq] or None, quantiles[nprob, nq] or
         None, hist[nq, nbins + 3] or None and, with ``chain_len`` (the rows of each chain), rhat, ess,
         lags [nq]); every number is the section calls', bit for bit.  models as for ``rasterize``."""
-        off = np.zeros(len(models) + 1, dtype=np.int64)
-        off[1:] = np.cumsum([len(m[0]) for m in models])
-        cat = [f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) for k in range(4)]
-        lens = np.ascontiguousarray(chain_len, dtype=np.int64).ravel() if chain_len is not None else None
+        off, cat = _pack_models(models, empty_ok=False)
+        lens = _chain_lens(chain_len)
 
         def call(vol):
             check(lib().td_rasterize_volume(self.h, len(models), ptr(off, _lib._pi64), *(ptr(c) for c in cat),
@@ -370,12 +385,10 @@ class TdContext:
                        want_values=False):
         """td_history_volume: ``volume`` on the samples of the histories (chain.History) where they lie;
         with ``convergence`` one history is one chain (one without samples is skipped)."""
-        histories = list(histories)
-        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
-        nm = sum(len(h) for h in histories)
+        hs, nm = _history_handles(histories)
 
         def call(vol):
-            check(lib().td_history_volume(self.h, hs, len(histories), vol), self.h)
+            check(lib().td_history_volume(self.h, hs, len(hs), vol), self.h)
 
         return self._volume(call, nm, qx, qy, qz, probs, bins, convergence, max_lag, want_values)
 
@@ -403,17 +416,9 @@ class TdContext:
         n = self.n
         res = dict(phi=np.empty(nmodels), mean=np.empty(n), std=np.empty(n), quantiles=None, hist=None,
                    ptS=np.empty((nmodels, n)) if want_values else None)
-        held = []
-        marg = cw = None
-        if len(np.ravel(probs)) or bins is not None:
-            marg, arrays, res["quantiles"], res["hist"] = self._marginals_want(n, probs, bins)
-            held.append(arrays)
-        if conv:
-            cw, arrays = self._convergence_want(n, max_lag, self.CONV_ALL)
-            res.update(arrays)
-        req = _lib.TdPredict(ptr(res["ptS"]), ptr(res["phi"]), ptr(res["mean"]), ptr(res["std"]),
-                             ctypes.addressof(marg) if marg is not None else None,
-                             ctypes.addressof(cw) if cw is not None else None)
+        marg, cw, entries, held = self._stat_wants(n, probs, bins, conv, max_lag)
+        res.update(entries)
+        req = _lib.TdPredict(ptr(res["ptS"]), ptr(res["phi"]), ptr(res["mean"]), ptr(res["std"]), marg, cw)
         call(ctypes.byref(req))
         del held
         return res
@@ -426,11 +431,8 @@ class TdContext:
         ptS[nmodels, n] or None).  Row k of ptS and phi[k] are ``evaluate`` of model k, bit for bit; the
         statistics are ``rasterize`` / ``marginals`` / ``convergence`` of the matrix ptS.  models as for
         ``rasterize``."""
-        off = np.zeros(len(models) + 1, dtype=np.int64)
-        off[1:] = np.cumsum([len(m[0]) for m in models])
-        cat = [f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) if len(models) else np.zeros(0)
-               for k in range(4)]
-        lens = np.ascontiguousarray(chain_len, dtype=np.int64).ravel() if chain_len is not None else None
+        off, cat = _pack_models(models)
+        lens = _chain_lens(chain_len)
 
         def call(req):
             check(lib().td_rasterize_predict(self.h, len(models), ptr(off, _lib._pi64), *(ptr(c) for c in cat),
@@ -442,12 +444,10 @@ class TdContext:
         """td_history_predict: ``predict`` on the samples of the histories (chain.History) where they lie;
         the histories may have been recorded on another context of this device.  With ``convergence`` one
         history is one chain (one without samples is skipped)."""
-        histories = list(histories)
-        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
-        nm = sum(len(h) for h in histories)
+        hs, nm = _history_handles(histories)
 
         def call(req):
-            check(lib().td_history_predict(self.h, hs, len(histories), req), self.h)
+            check(lib().td_history_predict(self.h, hs, len(hs), req), self.h)
 
         return self._predict(call, nm, probs, bins, convergence, max_lag, want_values)
 
@@ -496,10 +496,7 @@ class TdContext:
         target_std[T]); rows: the points, then the series.  cov = sum((v - mean)(a - target_mean)) / (M - 1) in
         ``rasterize``'s association without FMA, corr = cov / (std * target_std), unclamped.  Any number of
         nodes, swept slab by slab as by ``volume``.  models as for ``rasterize``."""
-        off = np.zeros(len(models) + 1, dtype=np.int64)
-        off[1:] = np.cumsum([len(m[0]) for m in models])
-        cat = [f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) if len(models) else np.zeros(0)
-               for k in range(4)]
+        off, cat = _pack_models(models)
 
         def call(req):
             check(lib().td_rasterize_covariance(self.h, len(models), ptr(off, _lib._pi64), *(ptr(c) for c in cat), req),
@@ -511,12 +508,10 @@ class TdContext:
         """td_history_covariance: ``covariance`` on the samples of the histories (chain.History) where they
         lie, history by history (one without samples is skipped); they may have been recorded on another
         context of this device."""
-        histories = list(histories)
-        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
-        nm = sum(len(h) for h in histories)
+        hs, nm = _history_handles(histories)
 
         def call(req):
-            check(lib().td_history_covariance(self.h, hs, len(histories), req), self.h)
+            check(lib().td_history_covariance(self.h, hs, len(hs), req), self.h)
 
         return self._covariance(call, nm, qx, qy, qz, targets, series, want)
 
@@ -570,10 +565,7 @@ class TdContext:
         coordinate.  ``want``: the subset of IFACE_ALL to compute ("stats": mean and std); what is not asked
         for, and exceed without thresholds, is None.  Any number of nodes, swept slab by slab as by ``volume``
         with the halo of the forward neighbours.  models as for ``rasterize``."""
-        off = np.zeros(len(models) + 1, dtype=np.int64)
-        off[1:] = np.cumsum([len(m[0]) for m in models])
-        cat = [f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) if len(models) else np.zeros(0)
-               for k in range(4)]
+        off, cat = _pack_models(models)
 
         def call(req):
             check(lib().td_rasterize_interfaces(self.h, len(models), ptr(off, _lib._pi64), *(ptr(c) for c in cat), req),
@@ -585,11 +577,10 @@ class TdContext:
         """td_history_interfaces: ``interfaces`` on the samples of the histories (chain.History) where they lie,
         history by history (one without samples is skipped); they may have been recorded on another context of
         this device."""
-        histories = list(histories)
-        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
+        hs, _ = _history_handles(histories, count=False)
 
         def call(req):
-            check(lib().td_history_interfaces(self.h, hs, len(histories), req), self.h)
+            check(lib().td_history_interfaces(self.h, hs, len(hs), req), self.h)
 
         return self._interfaces(call, xs, ys, zs, thresholds, want)
 
@@ -616,18 +607,11 @@ class TdContext:
             raise ValueError("reg_off must hold nreg + 1 >= 2 offsets")
         res = dict(series=np.empty((nmodels, R)), weight=np.empty(R), mean=np.empty(R), std=np.empty(R),
                    greater=np.empty((R, R), dtype=np.int64) if greater else None, quantiles=None, hist=None)
-        held = []
-        marg = cw = None
-        if len(np.ravel(probs)) or bins is not None:
-            marg, arrays, res["quantiles"], res["hist"] = self._marginals_want(R, probs, bins)
-            held.append(arrays)
-        if conv:
-            cw, arrays = self._convergence_want(R, max_lag, self.CONV_ALL)
-            res.update(arrays)
+        marg, cw, entries, held = self._stat_wants(R, probs, bins, conv, max_lag)
+        res.update(entries)
         req = _lib.TdRegions(ptr(px), ptr(py), ptr(pz), ptr(wv), npts, ptr(off, _lib._pi64), R, int(bool(normalize)),
                              ptr(res["series"]), ptr(res["weight"]), ptr(res["mean"]), ptr(res["std"]),
-                             ptr(res["greater"], _lib._pi64), ctypes.addressof(marg) if marg is not None else None,
-                             ctypes.addressof(cw) if cw is not None else None)
+                             ptr(res["greater"], _lib._pi64), marg, cw)
         call(ctypes.byref(req))
         del held
         return res
@@ -643,11 +627,8 @@ class TdContext:
         series[m, b] (None unless ``greater``); quantiles[nprob, R] or None; hist[R, nbins + 3] or None; with ``chain_len`` (the rows of
         each chain) rhat, ess, lags [R]) -- the statistics are ``volume``'s with the regions in the place of the
         nodes.  Any number of points, swept slab by slab as by ``volume``.  models as for ``rasterize``."""
-        off = np.zeros(len(models) + 1, dtype=np.int64)
-        off[1:] = np.cumsum([len(m[0]) for m in models])
-        cat = [f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) if len(models) else np.zeros(0)
-               for k in range(4)]
-        lens = np.ascontiguousarray(chain_len, dtype=np.int64).ravel() if chain_len is not None else None
+        off, cat = _pack_models(models)
+        lens = _chain_lens(chain_len)
 
         def call(req):
             check(lib().td_rasterize_regions(self.h, len(models), ptr(off, _lib._pi64), *(ptr(c) for c in cat),
@@ -661,12 +642,10 @@ class TdContext:
         """td_history_regions: ``regions`` on the samples of the histories (chain.History) where they lie, history
         by history (one without samples is skipped); they may have been recorded on another context of this
         device.  With ``convergence`` one history is one chain."""
-        histories = list(histories)
-        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
-        nm = sum(len(h) for h in histories)
+        hs, nm = _history_handles(histories)
 
         def call(req):
-            check(lib().td_history_regions(self.h, hs, len(histories), req), self.h)
+            check(lib().td_history_regions(self.h, hs, len(hs), req), self.h)
 
         return self._regions(call, nm, px, py, pz, reg_off, w, normalize, probs, bins, convergence, max_lag, greater)
 
@@ -688,20 +667,13 @@ class TdContext:
                    above=np.empty(npts, dtype=np.int64), dmean=np.empty(npts), dstd=np.empty(npts),
                    series=np.empty((nmodels, R)), weight=np.empty(R), mean=np.empty(R), std=np.empty(R), quantiles=None,
                    hist=None)
-        held = []
-        marg = cw = None
-        if len(np.ravel(probs)) or bins is not None:
-            marg, arrays, res["quantiles"], res["hist"] = self._marginals_want(R, probs, bins)
-            held.append(arrays)
-        if conv:
-            cw, arrays = self._convergence_want(R, max_lag, self.CONV_ALL)
-            res.update(arrays)
+        marg, cw, entries, held = self._stat_wants(R, probs, bins, conv, max_lag)
+        res.update(entries)
         i64 = _lib._pi64
         req = _lib.TdRecovery(ptr(px), ptr(py), ptr(pz), ptr(wv), npts, ptr(off, i64), R, ptr(tr), int(bool(normalize)),
                               ptr(res["below"], i64), ptr(res["equal"], i64), ptr(res["above"], i64), ptr(res["dmean"]),
                               ptr(res["dstd"]), ptr(res["series"]), ptr(res["weight"]), ptr(res["mean"]), ptr(res["std"]),
-                              ctypes.addressof(marg) if marg is not None else None,
-                              ctypes.addressof(cw) if cw is not None else None)
+                              marg, cw)
         call(ctypes.byref(req))
         del held
         return res
@@ -718,11 +690,8 @@ class TdContext:
         [nprob, R] or None, hist[R, nbins + 3] or None and, with ``chain_len``, rhat, ess, lags [R] of the series, as
         ``regions`` gives them).  Any number of points, swept slab by slab as by ``volume``.  models as for
         ``rasterize``."""
-        off = np.zeros(len(models) + 1, dtype=np.int64)
-        off[1:] = np.cumsum([len(m[0]) for m in models])
-        cat = [f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) if len(models) else np.zeros(0)
-               for k in range(4)]
-        lens = np.ascontiguousarray(chain_len, dtype=np.int64).ravel() if chain_len is not None else None
+        off, cat = _pack_models(models)
+        lens = _chain_lens(chain_len)
 
         def call(req):
             check(lib().td_rasterize_recovery(self.h, len(models), ptr(off, _lib._pi64), *(ptr(c) for c in cat),
@@ -736,12 +705,10 @@ class TdContext:
         """td_history_recovery: ``recovery`` on the samples of the histories (chain.History) where they lie, history
         by history (one without samples is skipped); they may have been recorded on another context of this
         device.  With ``convergence`` one history is one chain."""
-        histories = list(histories)
-        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
-        nm = sum(len(h) for h in histories)
+        hs, nm = _history_handles(histories)
 
         def call(req):
-            check(lib().td_history_recovery(self.h, hs, len(histories), req), self.h)
+            check(lib().td_history_recovery(self.h, hs, len(hs), req), self.h)
 
         return self._recovery(call, nm, px, py, pz, truth, reg_off, w, normalize, probs, bins, convergence, max_lag)
 
@@ -778,19 +745,12 @@ class TdContext:
                    orphans=np.empty(nmodels, dtype=np.int64), mean=np.empty(nq) if nq else None,
                    std=np.empty(nq) if nq else None, values=np.empty((nmodels, nq)) if want_values else None,
                    exceed=np.empty((len(thr), nq), dtype=np.int64) if len(thr) else None, quantiles=None, hist=None)
-        held = []
-        marg = cw = None
-        if len(np.ravel(probs)) or bins is not None:
-            marg, arrays, res["quantiles"], res["hist"] = self._marginals_want(nq, probs, bins)
-            held.append(arrays)
-        if conv:
-            cw, arrays = self._convergence_want(nq, max_lag, self.CONV_ALL)
-            res.update(arrays)
+        marg, cw, entries, held = self._stat_wants(nq, probs, bins, conv, max_lag)
+        res.update(entries)
         req = _lib.TdSupport(ptr(wv), ptr(qx), ptr(qy), ptr(qz), nq, ptr(thr) if len(thr) else None, len(thr),
                              ptr(res["cell"]), ptr(res["count"], _lib._pi64), ptr(res["barren"], _lib._pi64),
                              ptr(res["orphans"], _lib._pi64), ptr(res["values"]), ptr(res["mean"]), ptr(res["std"]),
-                             ptr(res["exceed"], _lib._pi64), ctypes.addressof(marg) if marg is not None else None,
-                             ctypes.addressof(cw) if cw is not None else None)
+                             ptr(res["exceed"], _lib._pi64), marg, cw)
         call(ctypes.byref(req))
         del held
         return res
@@ -807,11 +767,8 @@ class TdContext:
         quantiles[nprob, nq] or None, hist[nq, nbins + 3] or None, with ``chain_len`` rhat, ess, lags [nq]).
         ``want_cells=False`` leaves cell and count None (16 bytes per cell of every model stay on the device).
         models: list of (x, y, z[, zeta]) cell arrays; zeta is not read."""
-        off = np.zeros(len(models) + 1, dtype=np.int64)
-        off[1:] = np.cumsum([len(m[0]) for m in models])
-        cat = [f64(np.concatenate([np.asarray(m[k], dtype=np.float64) for m in models])) if len(models) else np.zeros(0)
-               for k in range(3)]
-        lens = np.ascontiguousarray(chain_len, dtype=np.int64).ravel() if chain_len is not None else None
+        off, cat = _pack_models(models, ncomp=3)
+        lens = _chain_lens(chain_len)
 
         def call(req):
             check(lib().td_rasterize_support(self.h, len(models), ptr(off, _lib._pi64), *(ptr(c) for c in cat),
@@ -826,12 +783,12 @@ class TdContext:
         by history (one without samples is skipped); they may have been recorded on another context of this
         device.  With ``convergence`` one history is one chain."""
         histories = list(histories)
-        hs = (ctypes.c_void_p * len(histories))(*[h.h for h in histories])
+        hs, _ = _history_handles(histories, count=False)
         counts = [h.count() for h in histories]  # (samples, cells used)
         nm, total = sum(c[0] for c in counts), sum(c[1] for c in counts)
 
         def call(req):
-            check(lib().td_history_support(self.h, hs, len(histories), req), self.h)
+            check(lib().td_history_support(self.h, hs, len(hs), req), self.h)
 
         return self._support(call, nm, total, w, qx, qy, qz, thresholds, probs, bins, convergence, max_lag, want_values,
                              want_cells)

@@ -147,6 +147,18 @@ def _chains(model_hist):
     return model_hist, [len(model_hist)]
 
 
+def _conv_summary(rhat, ess, lags, lens):
+    """The ``summary`` of ``convergence_maps`` over the columns of rhat, ess and lags; ``lens``: the chains' lengths."""
+    with np.errstate(invalid="ignore"):
+        return {
+            "rhat_max": float(np.nanmax(rhat)) if not np.all(np.isnan(rhat)) else float("nan"),
+            "ess_min": float(np.nanmin(ess)) if not np.all(np.isnan(ess)) else float("nan"),
+            "frac_rhat_above_1_01": float(np.mean(rhat > 1.01)),
+            "frac_capped": float(np.mean(lags < 0)),
+            "nan_columns": int(np.sum(np.isnan(rhat) | np.isnan(ess))),
+            "n": min(lens) // 2, "m": 2 * len(lens)}
+
+
 def convergence_maps(model_hist, dataStruct, TD_parameters, max_lag=0):
     """Whether the maps of ``plot_model_hist`` / ``credible_maps`` can be trusted: per node of the same
     sections (m[i, j] orientation) ``rhat``, the split Gelman-Rubin statistic over the chains' halves,
@@ -170,15 +182,7 @@ def convergence_maps(model_hist, dataStruct, TD_parameters, max_lag=0):
         else:
             r = ctx.convergence_models([m.cells() for m in models], lens, qx, qy, qz, max_lag)
         out = {f: r[f].reshape(shape).T.copy() for f in ("rhat", "ess", "lags", "mean", "std")}
-        rhat, ess = r["rhat"], r["ess"]
-        with np.errstate(invalid="ignore"):
-            out["summary"] = {
-                "rhat_max": float(np.nanmax(rhat)) if not np.all(np.isnan(rhat)) else float("nan"),
-                "ess_min": float(np.nanmin(ess)) if not np.all(np.isnan(ess)) else float("nan"),
-                "frac_rhat_above_1_01": float(np.mean(rhat > 1.01)),
-                "frac_capped": float(np.mean(r["lags"] < 0)),
-                "nan_columns": int(np.sum(np.isnan(rhat) | np.isnan(ess))),
-                "n": min(lens) // 2, "m": 2 * len(lens)}
+        out["summary"] = _conv_summary(r["rhat"], r["ess"], r["lags"], lens)
         maps[(axis, l0)] = out
     return maps
 
@@ -195,12 +199,7 @@ def posterior_volume(model_hist, dataStruct, TD_parameters, probs=(0.05, 0.5, 0.
     Same inputs as ``plot_model_hist`` (Models, nested lists, a ``History`` or a list of them); computed on
     the device slab by slab, whatever the lattice's size (td_rasterize_volume / td_history_volume)."""
     ctx = context_for(dataStruct)  # (TD_parameters: the siblings' signature; the lattice decides everything here)
-    xv, yv, zv = (np.asarray(v if v is not None else d, dtype=np.float64).ravel()
-                  for v, d in ((xs, dataStruct.xVec), (ys, dataStruct.yVec), (zs, dataStruct.zVec)))
-    shape = (len(zv), len(yv), len(xv))  # x fastest
-    qx = np.tile(xv, len(yv) * len(zv))
-    qy = np.tile(np.repeat(yv, len(xv)), len(zv))
-    qz = np.repeat(zv, len(xv) * len(yv))
+    xv, yv, zv, shape, qx, qy, qz = _lattice(dataStruct, xs, ys, zs)
     models, lens = _chains(model_hist)
     if _on_device(models):
         r = ctx.volume_history(models, qx, qy, qz, probs, bins, convergence, max_lag)
@@ -217,15 +216,7 @@ def posterior_volume(model_hist, dataStruct, TD_parameters, probs=(0.05, 0.5, 0.
     if r["hist"] is not None:
         out["hist"] = r["hist"].reshape(shape + (r["hist"].shape[1],)).transpose(2, 1, 0, 3).copy()
     if convergence:
-        rhat, ess = r["rhat"], r["ess"]
-        with np.errstate(invalid="ignore"):
-            out["summary"] = {
-                "rhat_max": float(np.nanmax(rhat)) if not np.all(np.isnan(rhat)) else float("nan"),
-                "ess_min": float(np.nanmin(ess)) if not np.all(np.isnan(ess)) else float("nan"),
-                "frac_rhat_above_1_01": float(np.mean(rhat > 1.01)),
-                "frac_capped": float(np.mean(r["lags"] < 0)),
-                "nan_columns": int(np.sum(np.isnan(rhat) | np.isnan(ess))),
-                "n": min(lens) // 2, "m": 2 * len(lens)}
+        out["summary"] = _conv_summary(r["rhat"], r["ess"], r["lags"], lens)
     return out
 
 
@@ -242,12 +233,7 @@ def posterior_covariance(model_hist, dataStruct, TD_parameters, targets, series=
     0.5 times node_volume, and ``x``, ``y``, ``z``.  Computed on the device slab by slab
     (td_rasterize_covariance / td_history_covariance)."""
     ctx = context_for(dataStruct)  # (TD_parameters: the siblings' signature; the lattice decides everything here)
-    xv, yv, zv = (np.asarray(v if v is not None else d, dtype=np.float64).ravel()
-                  for v, d in ((xs, dataStruct.xVec), (ys, dataStruct.yVec), (zs, dataStruct.zVec)))
-    shape = (len(zv), len(yv), len(xv))  # x fastest
-    qx = np.tile(xv, len(yv) * len(zv))
-    qy = np.tile(np.repeat(yv, len(xv)), len(zv))
-    qz = np.repeat(zv, len(xv) * len(yv))
+    xv, yv, zv, shape, qx, qy, qz = _lattice(dataStruct, xs, ys, zs)
     models, _ = _chains(model_hist)
     if _on_device(models):
         r = ctx.covariance_history(models, qx, qy, qz, targets, series)
@@ -276,10 +262,8 @@ def posterior_interfaces(model_hist, dataStruct, TD_parameters, thresholds=(5.0,
     ``y``, ``z``, ``thresholds``.  Same inputs as ``posterior_volume`` (Models, nested lists, a ``History`` or a
     list of them); computed on the device slab by slab (td_rasterize_interfaces / td_history_interfaces)."""
     ctx = context_for(dataStruct)  # (TD_parameters: the siblings' signature; the lattice decides everything here)
-    xv, yv, zv = (np.asarray(v if v is not None else d, dtype=np.float64).ravel()
-                  for v, d in ((xs, dataStruct.xVec), (ys, dataStruct.yVec), (zs, dataStruct.zVec)))
+    xv, yv, zv, shape, _, _, _ = _lattice(dataStruct, xs, ys, zs)
     thr = np.asarray(thresholds, dtype=np.float64).ravel()
-    shape = (len(zv), len(yv), len(xv))  # x fastest
     models, lens = _chains(model_hist)
     if _on_device(models):
         r = ctx.interfaces_history(models, xv, yv, zv, thr)
@@ -287,20 +271,15 @@ def posterior_interfaces(model_hist, dataStruct, TD_parameters, thresholds=(5.0,
         r = ctx.interfaces([m.cells() for m in models], xv, yv, zv, thr)
     M = sum(lens)
 
-    def grid(a):  # [..., nq] -> [..., nx, ny, nz]
-        lead = a.shape[:-1]
-        k = len(lead)
-        return a.reshape(lead + shape).transpose(tuple(range(k)) + (k + 2, k + 1, k)).copy()
-
     def share(c):
         return np.where(c < 0, np.nan, c / np.float64(M))
 
     out = {"x": xv, "y": yv, "z": zv, "thresholds": thr, "skipped": r["skipped"]}
     for f in ("count", "any", "jump", "mean", "std", "density"):
-        out[f] = grid(r[f])
+        out[f] = _grid(r[f], shape)
     out["prob"] = share(out["count"])
     out["prob_any"] = share(out["any"])
-    out["exceed"] = share(grid(r["exceed"])) if r["exceed"] is not None else np.empty((0, 3) + shape[::-1])
+    out["exceed"] = share(_grid(r["exceed"], shape)) if r["exceed"] is not None else np.empty((0, 3) + shape[::-1])
     out["density_per_model"] = out["density"] / np.float64(M)
     return out
 
@@ -391,8 +370,7 @@ def posterior_regions(model_hist, dataStruct, TD_parameters, regions, weights="v
     Same inputs as ``posterior_interfaces`` (Models, nested lists, a ``History`` or a list of them); computed on
     the device slab by slab (td_rasterize_regions / td_history_regions)."""
     ctx = context_for(dataStruct)  # (TD_parameters: the siblings' signature)
-    xv, yv, zv = (np.asarray(v if v is not None else d, dtype=np.float64).ravel()
-                  for v, d in ((xs, dataStruct.xVec), (ys, dataStruct.yVec), (zs, dataStruct.zVec)))
+    xv, yv, zv = _lattice(dataStruct, xs, ys, zs)[:3]
     names, px, py, pz, w, off = region_points(regions, xv, yv, zv, weights)
     models, lens = _chains(model_hist)
     if _on_device(models):
@@ -442,6 +420,13 @@ def _lattice(dataStruct, xs, ys, zs):
     return xv, yv, zv, (len(zv), len(yv), len(xv)), qx, qy, qz
 
 
+def _grid(a, shape):
+    """[..., nq] in the lattice's node order (``shape``, x fastest) -> [..., nx, ny, nz]"""
+    lead = a.shape[:-1]
+    k = len(lead)
+    return a.reshape(lead + shape).transpose(tuple(range(k)) + (k + 2, k + 1, k)).copy()
+
+
 def posterior_support(model_hist, dataStruct, TD_parameters, weights="tstar", thresholds=(0.0,), probs=None, bins=None,
                       convergence=False, xs=None, ys=None, zs=None):
     """Did the data say anything about this node, or is it the prior?  A Voronoi cell that owns no ray point does
@@ -470,21 +455,15 @@ def posterior_support(model_hist, dataStruct, TD_parameters, weights="tstar", th
                         want_cells=False)
         cells = np.array([len(m.cells()[0]) for m in models], dtype=np.int64)
     M = sum(lens)
-
-    def grid(a):  # [..., nq] -> [..., nx, ny, nz]
-        lead = a.shape[:-1]
-        k = len(lead)
-        return a.reshape(lead + shape).transpose(tuple(range(k)) + (k + 2, k + 1, k)).copy()
-
     out = {"x": xv, "y": yv, "z": zv, "thresholds": thr, "barren": r["barren"], "orphans": r["orphans"], "cells": cells}
     with np.errstate(invalid="ignore", divide="ignore"):
         out["barren_share"] = r["barren"] / cells.astype(np.float64)
     for f in ("mean", "std") + (("rhat", "ess", "lags") if convergence else ()):
-        out[f] = grid(r[f])
-    out["exceed"] = grid(r["exceed"]) if r["exceed"] is not None else np.empty((0,) + shape[::-1], dtype=np.int64)
+        out[f] = _grid(r[f], shape)
+    out["exceed"] = _grid(r["exceed"], shape) if r["exceed"] is not None else np.empty((0,) + shape[::-1], dtype=np.int64)
     out["share"] = out["exceed"] / np.float64(M)
     if r["quantiles"] is not None:
-        out["quantiles"] = grid(r["quantiles"])
+        out["quantiles"] = _grid(r["quantiles"], shape)
     if r["hist"] is not None:
         out["hist"] = r["hist"].reshape(shape + (r["hist"].shape[1],)).transpose(2, 1, 0, 3).copy()
     return out
@@ -620,15 +599,7 @@ def posterior_recovery(model_hist, dataStruct, TD_parameters, truth, regions=Non
         out["msd_hist"] = r["hist"][:R]
     if convergence:
         rhat, ess, lags = r["rhat"][:R], r["ess"][:R], r["lags"][:R]
-        out.update(rhat=rhat, ess=ess, lags=lags)
-        with np.errstate(invalid="ignore"):
-            out["summary"] = {
-                "rhat_max": float(np.nanmax(rhat)) if not np.all(np.isnan(rhat)) else float("nan"),
-                "ess_min": float(np.nanmin(ess)) if not np.all(np.isnan(ess)) else float("nan"),
-                "frac_rhat_above_1_01": float(np.mean(rhat > 1.01)),
-                "frac_capped": float(np.mean(lags < 0)),
-                "nan_columns": int(np.sum(np.isnan(rhat) | np.isnan(ess))),
-                "n": min(lens) // 2, "m": 2 * len(lens)}
+        out.update(rhat=rhat, ess=ess, lags=lags, summary=_conv_summary(rhat, ess, lags, lens))
     return out
 
 
@@ -664,16 +635,8 @@ def posterior_predictive(model_hist, dataStruct, TD_parameters, probs=(0.05, 0.5
     if values:
         out["ptS"] = r["ptS"]
     if convergence:
-        rhat, ess = r["rhat"], r["ess"]
-        out.update(rhat=rhat, ess=ess, lags=r["lags"])
-        with np.errstate(invalid="ignore"):
-            out["summary"] = {
-                "rhat_max": float(np.nanmax(rhat)) if not np.all(np.isnan(rhat)) else float("nan"),
-                "ess_min": float(np.nanmin(ess)) if not np.all(np.isnan(ess)) else float("nan"),
-                "frac_rhat_above_1_01": float(np.mean(rhat > 1.01)),
-                "frac_capped": float(np.mean(r["lags"] < 0)),
-                "nan_columns": int(np.sum(np.isnan(rhat) | np.isnan(ess))),
-                "n": min(lens) // 2, "m": 2 * len(lens)}
+        out.update(rhat=r["rhat"], ess=r["ess"], lags=r["lags"],
+                   summary=_conv_summary(r["rhat"], r["ess"], r["lags"], lens))
     return out
 
 
