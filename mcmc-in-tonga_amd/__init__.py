@@ -22,8 +22,8 @@ from .forward import Interpolation, TdContext, context_for, evaluate, v_nearest 
 from .tempering import Exchange, NativeComm, TemperingLadder, decide_swaps, geometric_ladder  # noqa: F401
 from .posterior import (box_region, checkerboard_model, convergence_maps, credible_maps, depth_layers,  # noqa: F401
                         model_distributions, plot_model_hist, posterior_covariance, posterior_interfaces,
-                        posterior_predictive, posterior_recovery, posterior_regions, posterior_support, posterior_volume,
-                        ray_density, region_points, section, support_weights, synthetic_data, trace_diagnostics,
-                        voxel_weights)
+                        posterior_predictive, posterior_recovery, posterior_regions, posterior_resolution,
+                        posterior_support, posterior_volume, ray_density, region_points, resolution_offsets, section,
+                        support_weights, synthetic_data, trace_diagnostics, voxel_weights)
 from .sharded import RayShardedContext, ray_points, shard_rays, sub_datastruct  # noqa: F401
 from . import jld  # noqa: F401  (save/load model.jld, main_inversion.jl:18)

@@ -143,6 +143,24 @@ SIGNATURES_RECOVERY = {
     "td_history_recovery": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, ctypes.POINTER(TdRecovery)]),
 }
 
+
+class TdResolution(ctypes.Structure):
+    """td_resolution (include/tdstar_resolution.h); the arrays as plain addresses (ptr())."""
+    _fields_ = [("xs", _vp), ("ys", _vp), ("zs", _vp), ("nx", _i64), ("ny", _i64), ("nz", _i64), ("off", _vp),
+                ("noff", _i64), ("threshold", _d), ("weights", _vp), ("cov_out", _vp), ("corr_out", _vp),
+                ("footprint_out", _vp), ("run_out", _vp), ("extent_out", _vp), ("censored_out", _vp), ("mean_out", _vp),
+                ("std_out", _vp)]
+
+
+# name -> (restype, argtypes); every symbol declared in include/tdstar_resolution.h, which tdstar.h does not include
+# (applied by lib() as SIGNATURES is)
+SIGNATURES_RESOLUTION = {
+    "td_rasterize_resolution": (ctypes.c_int, [_vp, _i64, _pi64, _pd, _pd, _pd, _pd, ctypes.POINTER(TdResolution)]),
+    "td_history_resolution": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, ctypes.POINTER(TdResolution)]),
+    "tdt_resolution_plan": (ctypes.c_int, [_i64, _i64, _i64, _i64, _i64, _pi64]),
+    "tdt_set_resolution": (ctypes.c_int, [_vp, _i64, ctypes.c_int]),
+}
+
 # name -> (restype, argtypes); every symbol declared in include/tdstar.h and include/tdstar_testing.h
 SIGNATURES = {
     "td_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _pd, _pd, _pd, _pd, _pd, _i64, _i64, _pd, _pd]),
@@ -293,7 +311,8 @@ def lib():
                               "(hipcc --offload-arch=gfx950); there is no CPU fallback")
         L = ctypes.CDLL(LIB_PATH)
         older = "TD_LIB_PATH" in os.environ  # (an A/B against an older build: newer testing hooks may be absent)
-        later = dict(SIGNATURES_INTERFACES, **SIGNATURES_REGIONS, **SIGNATURES_SUPPORT, **SIGNATURES_RECOVERY)  # (the headers of their own)
+        later = dict(SIGNATURES_INTERFACES, **SIGNATURES_REGIONS, **SIGNATURES_SUPPORT, **SIGNATURES_RECOVERY,
+                     **SIGNATURES_RESOLUTION)  # (the headers of their own)
         for name, (res, args) in list(SIGNATURES.items()) + list(later.items()):
             if older and (name.startswith("tdt_") or name in later) and not hasattr(L, name):
                 continue

@@ -584,6 +584,84 @@ class TdContext:
 
         return self._interfaces(call, xs, ys, zs, thresholds, want)
 
+    RES_SUMMARY = ("footprint", "run", "extent", "censored", "stats")
+    RES_ALL = ("cov", "corr") + RES_SUMMARY
+
+    @staticmethod
+    def resolution_plan(nmodels, nq, reach, budget=0, forced=0):
+        """(ns: the nodes of a block, R: the resident blocks, the blocks) of a ``resolution`` call on ``nq`` nodes
+        whose largest flat offset is ``reach`` (budget in bytes of the resident blocks, 0: 2 GiB); needs no GPU."""
+        out = np.zeros(3, dtype=np.int64)
+        check(lib().tdt_resolution_plan(int(nmodels), int(nq), int(reach), int(budget), int(forced), ptr(out, _lib._pi64)))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    RES_FORM_KEPT, RES_FORM_PLAIN, RES_FORM_XRUNS = 0, 1, 2
+
+    def set_resolution(self, budget=0, form=RES_FORM_KEPT):
+        """``resolution``'s budget in bytes of the resident blocks (0: 2 GiB) and the form of its pair kernel
+        (RES_FORM_PLAIN: one partner load per offset; RES_FORM_XRUNS: a run of offsets that differ in di alone is
+        served from one staged segment; RES_FORM_KEPT: runs of two offsets and more as x-runs, the lone ones plain).  Same
+        answer."""
+        check(lib().tdt_set_resolution(self.h, int(budget), int(form)), self.h)
+
+    def _resolution(self, call, xs, ys, zs, offsets, threshold, weights, want):
+        """The td_resolution request around ``call(byref(req))`` -> dict of the flat outputs."""
+        xs, ys, zs = (f64(np.ravel(a)) for a in (xs, ys, zs))
+        off = np.ascontiguousarray(np.reshape(offsets, (-1, 3)), dtype=np.int32)
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not set(want) <= set(self.RES_ALL):
+            raise ValueError("want: a subset of %s" % (self.RES_ALL,))
+        nx, ny, nz, noff = len(xs), len(ys), len(zs), len(off)
+        nq = nx * ny * nz
+        wts = None
+        if weights is not None:
+            wts = f64(np.ravel(weights))
+            if len(wts) != nq:
+                raise ValueError("weights must hold nx ny nz = %d numbers, x fastest; got %d" % (nq, len(wts)))
+        res = dict(cov=np.empty((noff, nq)) if "cov" in want else None, corr=np.empty((noff, nq)) if "corr" in want else None,
+                   footprint=np.empty(nq) if "footprint" in want else None,
+                   run=np.empty((3, 2, nq), dtype=np.int32) if "run" in want else None,
+                   extent=np.empty((3, nq)) if "extent" in want else None,
+                   censored=np.empty(nq, dtype=np.int32) if "censored" in want else None,
+                   mean=np.empty(nq) if "stats" in want else None, std=np.empty(nq) if "stats" in want else None)
+        i32 = _lib._pi32
+        req = _lib.TdResolution(ptr(xs), ptr(ys), ptr(zs), nx, ny, nz, ptr(off, i32) if noff else None, noff, float(threshold),
+                                ptr(wts), ptr(res["cov"]), ptr(res["corr"]), ptr(res["footprint"]), ptr(res["run"], i32),
+                                ptr(res["extent"]), ptr(res["censored"], i32), ptr(res["mean"]), ptr(res["std"]))
+        call(ctypes.byref(req))
+        return res
+
+    def resolution(self, models, xs, ys, zs, offsets, threshold=0.5, weights=None, want=RES_SUMMARY):
+        """td_rasterize_resolution: for every node n of the lattice ``xs`` x ``ys`` x ``zs`` (n = i + nx (j + ny k), x
+        fastest) the correlation, over the models, of zeta there with zeta at each neighbour n + f(o) of the window
+        ``offsets`` [noff, 3] = forward (di, dj, dk) (``posterior.resolution_offsets``), and what it reduces to ->
+        dict of flat arrays: cov[noff, nq], corr[noff, nq] (NaN where the pair leaves the lattice; ``covariance``'s
+        numbers for a point target at n, bit for bit), footprint[nq] the sum of ``weights`` [nq] (None: 1.0 each) over
+        the node and the neighbours, forwards and backwards, tied to it at corr >= ``threshold``, run[3, 2, nq]
+        (int32) the contiguous steps along +a / -a that pass, extent[3, nq] the distance between the ends of the two
+        runs, censored[nq] (int32; bit 2a / 2a + 1: the run along +a / -a ended on the lattice's or the window's edge
+        and not on a failing correlation), mean[nq], std[nq] (``volume``'s).  ``want``: the subset of RES_ALL to
+        compute ("stats": mean and std); what is not asked for is None.  Every node is swept once, in a ring of
+        blocks (``resolution_plan``).  models as for ``rasterize``."""
+        off, cat = _pack_models(models)
+
+        def call(req):
+            check(lib().td_rasterize_resolution(self.h, len(models), ptr(off, _lib._pi64), *(ptr(c) for c in cat), req),
+                  self.h)
+
+        return self._resolution(call, xs, ys, zs, offsets, threshold, weights, want)
+
+    def resolution_history(self, histories, xs, ys, zs, offsets, threshold=0.5, weights=None, want=RES_SUMMARY):
+        """td_history_resolution: ``resolution`` on the samples of the histories (chain.History) where they lie,
+        history by history (one without samples is skipped); they may have been recorded on another context of
+        this device."""
+        hs, _ = _history_handles(histories, count=False)
+
+        def call(req):
+            check(lib().td_history_resolution(self.h, hs, len(hs), req), self.h)
+
+        return self._resolution(call, xs, ys, zs, offsets, threshold, weights, want)
+
     @staticmethod
     def regions_plan(nmodels, npoints, budget=0, forced=0):
         """(the points a slab sweeps, slabs) of a ``regions`` call on ``npoints`` points (budget in bytes, 0:

@@ -284,6 +284,64 @@ def posterior_interfaces(model_hist, dataStruct, TD_parameters, thresholds=(5.0,
     return out
 
 
+def resolution_offsets(lags=(2, 1, 2), window="box"):
+    """The window of ``posterior_resolution`` as forward lattice offsets [noff, 3] (di, dj, dk), int32.  ``lags`` =
+    (Lx, Ly, Lz) >= 0.  ``window="axes"``: (l, 0, 0), l = 1 .. Lx, then (0, l, 0), then (0, 0, l).  ``"box"``: every
+    forward offset (dk > 0, or dk == 0 and dj > 0, or dk == dj == 0 and di > 0) with abs(di) <= Lx, abs(dj) <= Ly, 0 <=
+    dk <= Lz -- the axes' offsets first, in that order, so that the runs can use them, then the others with di
+    fastest and dk slowest."""
+    Lx, Ly, Lz = (int(v) for v in lags)
+    if min(Lx, Ly, Lz) < 0:
+        raise ValueError("lags must be >= 0")
+    if window not in ("axes", "box"):
+        raise ValueError("window: 'axes' or 'box'")
+    out = [(l, 0, 0) for l in range(1, Lx + 1)] + [(0, l, 0) for l in range(1, Ly + 1)] + [(0, 0, l) for l in range(1, Lz + 1)]
+    if window == "box":
+        on_axis = set(out)
+        out += [(di, dj, dk) for dk in range(0, Lz + 1) for dj in range(-Ly, Ly + 1) for di in range(-Lx, Lx + 1)
+                if (dk, dj, di) > (0, 0, 0) and (di, dj, dk) not in on_axis]
+    return np.asarray(out, dtype=np.int32).reshape(-1, 3)
+
+
+def posterior_resolution(model_hist, dataStruct, TD_parameters, lags=(2, 1, 2), window="box", threshold=0.5, weights="volume",
+                         xs=None, ys=None, zs=None, want=None):
+    """The ensemble's point-spread function at EVERY node: how far from a node the models tie zeta together, in which
+    direction, and where that is unknown because the lattice or the window ends -- what ``posterior_covariance`` gives
+    at a handful of targets.  On the lattice ``xs`` x ``ys`` x ``zs`` (default: dataStruct.xVec / yVec / zVec), with
+    the window ``resolution_offsets(lags, window)``, -> dict: ``offsets`` [noff, 3]; ``corr``, ``cov`` [noff, nx, ny,
+    nz], the correlation and covariance of the node's zeta with the neighbour's at the offset (NaN where the pair
+    leaves the lattice), only when named in ``want``; ``footprint`` [nx, ny, nz], the weight of the node and of the
+    neighbours, forwards and backwards, with corr >= ``threshold`` (``weights="volume"``: ``voxel_weights``, km^3;
+    None: a count of nodes; an array [nx, ny, nz]); ``run`` [3, 2, nx, ny, nz], the contiguous steps along +a / -a that
+    pass; ``extent`` [3, nx, ny, nz], the distance between the two runs' ends; ``censored`` [nx, ny, nz] (bit 2a / 2a
+    + 1: the run along +a / -a ended on the lattice's or the window's edge, not on a failing correlation); ``mean``,
+    ``std`` (``posterior_volume``'s); ``x``, ``y``, ``z``, ``threshold``.  ``want`` (default: everything but corr and
+    cov): the subset of TdContext.RES_ALL to compute; an output that was not asked for is None.  Same inputs as
+    ``posterior_volume``; every node is swept once on the device (td_rasterize_resolution / td_history_resolution)."""
+    ctx = context_for(dataStruct)  # (TD_parameters: the siblings' signature; the lattice decides everything here)
+    xv, yv, zv, shape, _, _, _ = _lattice(dataStruct, xs, ys, zs)
+    off = resolution_offsets(lags, window)
+    if isinstance(weights, str):
+        if weights != "volume":
+            raise ValueError("weights: 'volume', None or an array [nx, ny, nz]")
+        weights = voxel_weights(xv, yv, zv)
+    if weights is not None:
+        w = np.asarray(weights, dtype=np.float64)
+        if w.shape != shape[::-1]:
+            raise ValueError("weights must be [nx, ny, nz] = %s; got %s" % (shape[::-1], w.shape))
+        weights = w.transpose(2, 1, 0).ravel()  # x fastest
+    want = ctx.RES_SUMMARY if want is None else want
+    models, _ = _chains(model_hist)
+    if _on_device(models):
+        r = ctx.resolution_history(models, xv, yv, zv, off, threshold, weights, want)
+    else:
+        r = ctx.resolution([m.cells() for m in models], xv, yv, zv, off, threshold, weights, want)
+    out = {"x": xv, "y": yv, "z": zv, "offsets": off, "threshold": float(threshold)}
+    for f in ("corr", "cov", "footprint", "extent", "run", "censored", "mean", "std"):
+        out[f] = _grid(r[f], shape) if r[f] is not None else None
+    return out
+
+
 def voxel_weights(xs, ys, zs):
     """The volume of every node's voxel, [nx, ny, nz]: (dx_i * dy_j) * dz_k.  Along an axis of n >= 2 nodes v the
     widths are the differences of the edges [v_0, the midpoints 0.5 (v_l + v_{l+1}) ..., v_{n-1}] (the end nodes
