@@ -20,8 +20,9 @@ from .data import (CONFIGS, ak135_slowness, box, interp1, load_data_Tonga, lonla
 from .defstruct import DataStruct, Model, Ray  # noqa: F401
 from .forward import Interpolation, TdContext, context_for, evaluate, v_nearest  # noqa: F401
 from .tempering import Exchange, NativeComm, TemperingLadder, decide_swaps, geometric_ladder  # noqa: F401
-from .posterior import (box_region, checkerboard_model, convergence_maps, credible_maps, depth_layers,  # noqa: F401
-                        model_distributions, plot_model_hist, posterior_covariance, posterior_interfaces,
+from .posterior import (box_region, checkerboard_model, compare_summary, convergence_maps, credible_maps,  # noqa: F401
+                        depth_layers, info_gain_bits, model_distributions, plot_model_hist, posterior_compare,
+                        posterior_covariance, posterior_interfaces,
                         posterior_predictive, posterior_recovery, posterior_regions, posterior_resolution,
                         posterior_support, posterior_volume, ray_density, region_points, resolution_offsets, section,
                         support_weights, synthetic_data, trace_diagnostics, voxel_weights)

@@ -161,6 +161,27 @@ SIGNATURES_RESOLUTION = {
     "tdt_set_resolution": (ctypes.c_int, [_vp, _i64, ctypes.c_int]),
 }
 
+
+class TdCompare(ctypes.Structure):
+    """td_compare (include/tdstar_compare.h); the arrays and the two optional requests as plain addresses (ptr(),
+    ctypes.addressof)."""
+    _fields_ = [("qx", _vp), ("qy", _vp), ("qz", _vp), ("nq", _i64), ("nexceed", _i64), ("scale", _vp), ("shift", _vp),
+                ("less_out", _vp), ("equal_out", _vp), ("greater_out", _vp), ("exceed_out", _vp), ("ks_plus_out", _vp),
+                ("ks_minus_out", _vp), ("ks_at_out", _vp), ("mean_a_out", _vp), ("std_a_out", _vp), ("mean_b_out", _vp),
+                ("std_b_out", _vp), ("marg_a", _vp), ("marg_b", _vp)]
+
+
+# name -> (restype, argtypes); every symbol declared in include/tdstar_compare.h, which tdstar.h does not include
+# (applied by lib() as SIGNATURES is)
+SIGNATURES_COMPARE = {
+    "td_rasterize_compare": (ctypes.c_int, [_vp, _i64, _pi64, _pd, _pd, _pd, _pd, _i64, _pi64, _pd, _pd, _pd, _pd,
+                                            ctypes.POINTER(TdCompare)]),
+    "td_history_compare": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, ctypes.POINTER(_vp), _i64,
+                                          ctypes.POINTER(TdCompare)]),
+    "td_compare_values": (ctypes.c_int, [_vp, _pd, _i64, _pd, _i64, _i64, ctypes.POINTER(TdCompare)]),
+    "tdt_set_compare_form": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+}
+
 # name -> (restype, argtypes); every symbol declared in include/tdstar.h and include/tdstar_testing.h
 SIGNATURES = {
     "td_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _pd, _pd, _pd, _pd, _pd, _i64, _i64, _pd, _pd]),
@@ -312,7 +333,7 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         older = "TD_LIB_PATH" in os.environ  # (an A/B against an older build: newer testing hooks may be absent)
         later = dict(SIGNATURES_INTERFACES, **SIGNATURES_REGIONS, **SIGNATURES_SUPPORT, **SIGNATURES_RECOVERY,
-                     **SIGNATURES_RESOLUTION)  # (the headers of their own)
+                     **SIGNATURES_RESOLUTION, **SIGNATURES_COMPARE)  # (the headers of their own)
         for name, (res, args) in list(SIGNATURES.items()) + list(later.items()):
             if older and (name.startswith("tdt_") or name in later) and not hasattr(L, name):
                 continue

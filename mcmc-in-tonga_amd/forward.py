@@ -790,6 +790,99 @@ class TdContext:
 
         return self._recovery(call, nm, px, py, pz, truth, reg_off, w, normalize, probs, bins, convergence, max_lag)
 
+    CMP_COUNTS, CMP_KS, CMP_STATS = "counts", "ks", "stats"
+    CMP_ALL = (CMP_COUNTS, CMP_KS, CMP_STATS)
+
+    def _compare(self, call, ncol, qx, qy, qz, exceed, probs, bins, want):
+        """The td_compare request around ``call(byref(req))`` -> dict of the outputs."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not set(want) <= set(self.CMP_ALL):
+            raise ValueError("want: a subset of %s" % (self.CMP_ALL,))
+        pairs = f64(np.reshape(np.asarray(exceed, dtype=np.float64), (-1, 2)))
+        scale, shift = f64(pairs[:, 0]), f64(pairs[:, 1])
+        ne = len(scale)
+        i64 = _lib._pi64
+        counts, ks, stats = (k in want for k in self.CMP_ALL)
+        cnt = lambda on: np.zeros(ncol, dtype=np.int64) if on else None  # noqa: E731
+        res = dict(less=cnt(counts), equal=cnt(counts), greater=cnt(counts),
+                   exceed=np.zeros((ne, ncol), dtype=np.int64) if ne else None, ks_plus=cnt(ks), ks_minus=cnt(ks),
+                   ks_at=np.full(ncol, np.nan) if ks else None)
+        for side in "ab":
+            res["mean_" + side], res["std_" + side] = (np.empty(ncol), np.empty(ncol)) if stats else (None, None)
+        held, marg = [], {}
+        for side in "ab":
+            m, mw, entries, keep = self._stat_wants(ncol, probs, bins, False, 0)
+            held.append(keep)
+            marg[side] = m
+            res["quantiles_" + side], res["hist_" + side] = entries["quantiles"], entries["hist"]
+        req = _lib.TdCompare(ptr(qx), ptr(qy), ptr(qz), ncol if qx is not None else 0, ne, ptr(scale) if ne else None,
+                             ptr(shift) if ne else None, ptr(res["less"], i64), ptr(res["equal"], i64), ptr(res["greater"], i64),
+                             ptr(res["exceed"], i64), ptr(res["ks_plus"], i64), ptr(res["ks_minus"], i64), ptr(res["ks_at"]),
+                             ptr(res["mean_a"]), ptr(res["std_a"]), ptr(res["mean_b"]), ptr(res["std_b"]), marg["a"], marg["b"])
+        call(ctypes.byref(req))
+        del held
+        return res
+
+    def compare(self, models_a, models_b, qx, qy, qz, exceed=(), probs=(), bins=None, want=CMP_ALL):
+        """td_rasterize_compare: one ensemble against another.  With a_i, b_j the nearest-cell values (``volume``'s) of
+        the models of side A and side B at a node -> dict, per node: less, equal, greater[nq] = the pairs (i, j) with
+        a_i <, ==, > b_j (IEEE: a NaN counts in nothing, -0.0 == 0.0); exceed[nexceed, nq] = the pairs with a_i > s_k *
+        b_j + t_k for ``exceed`` = [(s_k, t_k)], two rounded operations (None without pairs); ks_plus, ks_minus[nq] =
+        max(0, max of +-T) with T(x) = #{a <= x} MB - #{b <= x} MA over the values x of both sides, and ks_at[nq] the
+        smallest x at which abs(T) is largest (NaN where T is 0 throughout); mean_a, std_a, mean_b, std_b[nq],
+        quantiles_a, quantiles_b[nprob, nq] or None and hist_a, hist_b[nq, nbins + 3] or None: ``volume``'s of each
+        side alone, bit for bit.  All counts are int64 and exact.  ``want``: the subset of CMP_ALL to compute.  The two
+        sides are swept as one ensemble, slab by slab as by ``volume``; at most 16384 models a side.  models as for
+        ``rasterize``."""
+        offa, cata = _pack_models(models_a)
+        offb, catb = _pack_models(models_b)
+        qx, qy, qz = (f64(np.ravel(a)) for a in (qx, qy, qz))
+        if not (len(qy) == len(qz) == len(qx)):
+            raise ValueError("qx, qy and qz must have the same length")
+
+        def call(req):
+            check(lib().td_rasterize_compare(self.h, len(models_a), ptr(offa, _lib._pi64), *(ptr(c) for c in cata),
+                                             len(models_b), ptr(offb, _lib._pi64), *(ptr(c) for c in catb), req), self.h)
+
+        return self._compare(call, len(qx), qx, qy, qz, exceed, probs, bins, want)
+
+    def compare_history(self, histories_a, histories_b, qx, qy, qz, exceed=(), probs=(), bins=None, want=CMP_ALL):
+        """td_history_compare: ``compare`` on the samples of two lists of histories (chain.History) where they lie,
+        history by history (one without samples is skipped); they may have been recorded on another context of this
+        device."""
+        ha, _ = _history_handles(histories_a, count=False)
+        hb, _ = _history_handles(histories_b, count=False)
+        qx, qy, qz = (f64(np.ravel(a)) for a in (qx, qy, qz))
+        if not (len(qy) == len(qz) == len(qx)):
+            raise ValueError("qx, qy and qz must have the same length")
+
+        def call(req):
+            check(lib().td_history_compare(self.h, ha, len(ha), hb, len(hb), req), self.h)
+
+        return self._compare(call, len(qx), qx, qy, qz, exceed, probs, bins, want)
+
+    def compare_values(self, values_a, values_b, exceed=(), probs=(), bins=None, want=CMP_ALL):
+        """td_compare_values: ``compare`` on the columns of two host matrices ``values_a`` [MA, ncol] and ``values_b``
+        [MB, ncol] (or [MA], [MB]: one column) with no search: traces of phi or nCells, ``regions``' series, predicted
+        t*.  Every output has ncol columns."""
+        A, B = f64(values_a), f64(values_b)
+        A = A.reshape(-1, 1) if A.ndim == 1 else A
+        B = B.reshape(-1, 1) if B.ndim == 1 else B
+        if A.ndim != 2 or B.ndim != 2 or A.shape[1] != B.shape[1]:
+            raise ValueError("values_a [MA, ncol] and values_b [MB, ncol] must have the same columns")
+
+        def call(req):
+            check(lib().td_compare_values(self.h, ptr(A), A.shape[0], ptr(B), B.shape[0], A.shape[1], req), self.h)
+
+        return self._compare(call, A.shape[1], None, None, None, exceed, probs, bins, want)
+
+    @staticmethod
+    def set_compare_form(plain=False, sort_threads=0, count_threads=0):
+        """The columns the workgroups of ``compare``'s sort kernel take -- eight neighbouring ones per XCD (default), or
+        ``plain``: the column of the workgroup's index -- and the threads of a workgroup of its two kernels (a power of
+        two 64 .. 1024; 0: by the larger side).  Same answer.  Process-wide."""
+        check(lib().tdt_set_compare_form(int(bool(plain)), int(sort_threads), int(count_threads)))
+
     SUP_AUTO, SUP_LDS, SUP_GLOBAL = 0, 1, 2
 
     @staticmethod

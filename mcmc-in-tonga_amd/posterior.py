@@ -661,6 +661,82 @@ def posterior_recovery(model_hist, dataStruct, TD_parameters, truth, regions=Non
     return out
 
 
+def info_gain_bits(hist_a, hist_b, MA, MB):
+    """The Kullback-Leibler divergence of side A's histogram from side B's, in bits, per row of ``hist_a``, ``hist_b``
+    [..., nbins + 3] (``marginals``' slots: below lo, the bins, at or above hi, NaN) of ``MA`` and ``MB`` samples:
+    sum over the slots s of pA_s log2(pA_s / pB_s) with p_s = (c_s + 0.5) / (M + 0.5 (nbins + 3)), the add-a-half
+    estimate, which keeps an empty slot's term finite.  Formed on the host from the integer counts."""
+    ha, hb = np.asarray(hist_a, dtype=np.float64), np.asarray(hist_b, dtype=np.float64)
+    slots = ha.shape[-1]
+    pa = (ha + 0.5) / (np.float64(MA) + 0.5 * slots)
+    pb = (hb + 0.5) / (np.float64(MB) + 0.5 * slots)
+    return np.sum(pa * np.log2(pa / pb), axis=-1)
+
+
+def compare_summary(r, MA, MB):
+    """What ``posterior_compare`` derives from the integer outputs ``r`` of ``TdContext.compare`` (any shape) for sides
+    of ``MA`` and ``MB`` models -> dict: ``prob_greater`` = (greater + 0.5 equal) / (MA MB), ``prob_exceed`` = exceed /
+    (MA MB), ``ks`` = max(ks_plus, ks_minus) / (MA MB), ``ks_sign`` (+1 where ks_plus is the larger: A's CDF lies
+    above B's, A is the smaller; -1 where ks_minus is; 0 where they are equal), ``mean_diff`` = mean_a - mean_b and,
+    with histograms, ``info_gain_bits`` (``info_gain_bits``).  Entries whose inputs are None are left out."""
+    pairs = np.float64(MA) * np.float64(MB)
+    out = {}
+    if r.get("greater") is not None:
+        out["prob_greater"] = (r["greater"] + 0.5 * r["equal"]) / pairs
+    if r.get("exceed") is not None:
+        out["prob_exceed"] = r["exceed"] / pairs
+    if r.get("ks_plus") is not None:
+        out["ks"] = np.maximum(r["ks_plus"], r["ks_minus"]) / pairs
+        out["ks_sign"] = np.sign(r["ks_plus"] - r["ks_minus"]).astype(np.int8)
+    if r.get("mean_a") is not None:
+        out["mean_diff"] = r["mean_a"] - r["mean_b"]
+    if r.get("hist_a") is not None:
+        out["info_gain_bits"] = info_gain_bits(r["hist_a"], r["hist_b"], MA, MB)
+    return out
+
+
+def posterior_compare(model_hist_a, model_hist_b, dataStruct, TD_parameters, exceed=((1.0, 0.0),), probs=None, bins=None,
+                      xs=None, ys=None, zs=None):
+    """One ensemble against another, node by node: the posterior against a ``debug_prior=1`` ensemble (how far did the
+    data move the marginal?), a run against a run with other data or another prior, zeta_S against zeta_P.  Each
+    side as ``posterior_volume`` takes it (Models, nested lists, a ``History`` or a list of them, recorded on any
+    context of the device; where only one side is on the device its samples are read back), independent samples, at
+    most 16384 a side.  With a_i, b_j the two sides' values at a node, on the lattice ``xs`` x ``ys`` x ``zs``
+    (default dataStruct.xVec / yVec / zVec) -> dict of [nx, ny, nz] arrays: the exact pair counts ``less``, ``equal``,
+    ``greater`` (a_i <, ==, > b_j), ``exceed`` [npairs, ...] (a_i > s b_j + t for ``exceed`` = [(s, t)]: with zeta =
+    1000 / Q, (r, 0) asks for Q_B / Q_A > r), ``ks_plus``, ``ks_minus``; ``prob_greater`` = (greater + 0.5 equal) /
+    (MA MB), the probability of superiority (Mann-Whitney's U over MA MB); ``prob_exceed`` = exceed / (MA MB); ``ks`` =
+    max(ks_plus, ks_minus) / (MA MB), the two-sample Kolmogorov-Smirnov distance, ``ks_sign`` (+1: A's CDF lies
+    above, A is the smaller) and ``ks_at``, the smallest value at which it is reached (NaN where the two samples
+    have one CDF); ``mean_a``, ``std_a``, ``mean_b``, ``std_b`` (``posterior_volume``'s of each side, bit for bit)
+    and ``mean_diff``; with ``probs`` ``quantiles_a``, ``quantiles_b`` [nprob, ...]; with ``bins`` = (nbins, lo, hi)
+    ``hist_a``, ``hist_b`` [..., nbins + 3] and ``info_gain_bits`` = sum over the nbins + 3 slots s of pA_s log2(pA_s /
+    pB_s) with p_s = (c_s + 0.5) / (M + 0.5 (nbins + 3)), formed on the host from the integer histograms; ``x``,
+    ``y``, ``z``, ``MA``, ``MB``.  A p-value needs the effective sample sizes (``posterior_volume(convergence=True)``
+    per side) and is the caller's.  Computed on the device as one ensemble of MA + MB models, slab by slab
+    (td_rasterize_compare / td_history_compare)."""
+    ctx = context_for(dataStruct)  # (TD_parameters: the siblings' signature)
+    xv, yv, zv, shape, qx, qy, qz = _lattice(dataStruct, xs, ys, zs)
+    probs = () if probs is None else probs
+    (ma, la), (mb, lb) = _chains(model_hist_a), _chains(model_hist_b)
+    MA, MB = sum(la), sum(lb)
+    if _on_device(ma) and _on_device(mb):
+        r = ctx.compare_history(ma, mb, qx, qy, qz, exceed, probs, bins)
+    else:
+        ma, mb = ([m for h in s for m in h.read()] if _on_device(s) else s for s in (ma, mb))
+        r = ctx.compare([m.cells() for m in ma], [m.cells() for m in mb], qx, qy, qz, exceed, probs, bins)
+    out = {"x": xv, "y": yv, "z": zv, "MA": MA, "MB": MB}
+    r.update(compare_summary(r, MA, MB))
+    for f, a in r.items():
+        if a is None:
+            continue
+        if f in ("hist_a", "hist_b"):
+            out[f] = a.reshape(shape + (a.shape[1],)).transpose(2, 1, 0, 3).copy()
+        else:
+            out[f] = _grid(a, shape)
+    return out
+
+
 def posterior_predictive(model_hist, dataStruct, TD_parameters, probs=(0.05, 0.5, 0.95), bins=None, convergence=False,
                          values=False, max_lag=0):
     """Does the ensemble fit the data, ray by ray, and does it predict data it was not fitted to?  Every
