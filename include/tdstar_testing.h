@@ -81,16 +81,50 @@ int tdt_history_pack_chunk(void);
  * (pts: nq x {x, y, z}); mode 0: the whole query, 1: its loads only, 2: its arithmetic only.
  * out[0] = cycles, out[1] = unproven queries (full scans). */
 int tdt_chain_query_lat(td_chain *ch, const double *pts, int nq, int mode, int64_t out[4]);
-/* Each query's answer from the chain's grid search (mode 0: the LDS grid copy with the global first
- * bound; 6: the descriptor-reading form): squared distance, the winning cell's value, proven (1) or
- * left to the full scan (0). */
 /* The chain's phase-B tile filter on caller boxes (FP32, SoA: x of every tile, then y, then z), FP64 tile
  * maxima and FP64 queries (x, y, z each): hit[q * nt + t] = 1 if tile t passes for query q.  mode 0: the
  * filter of the HBM layout's super-tiles; 1: the LDS layout's tile pass (tile_may_hit2). */
 int tdt_tile_filter(const float *lo, const float *hi, const double *maxd, int nt, const double *queries, int nq,
                     int mode, uint8_t *hit);
+/* Each query's answer from the chain's grid search (mode 0: the LDS grid copy with the global first
+ * bound; 6: the descriptor-reading form): squared distance, the winning cell's value, proven (1) or
+ * left to the full scan (0). */
 int tdt_chain_query_answers(td_chain *ch, const double *pts, int nq, int mode, double *dist, double *value,
                             int32_t *proven);
+/* The same queries with a killed and a moved cell, as a death's, a move's and the drop-in path's queries run:
+ * kill[i] / moved[i] = 0-based Julia positions (-1: none), mapped to slots through the chain's order as
+ * k_chain_run maps them; slot moved is taken at msite[3 i .. 3 i + 2] with the value czeta[moved].  mode 0 and 6
+ * as above, 7: wave_nearest (the grid search, then the full scan of every slot if unproven).  pos[i] = the
+ * winner's 0-based Julia position (-1: no cell below the 1e9 sentinel; -2: a slot no position names).
+ * info = {nslots, cap, ncells, the grid's overflow flag}.  TD_ERR_ARG before any launch for a position
+ * outside [-1, ncells).  Needs a GPU. */
+int tdt_chain_nearest(td_chain *ch, const double *pts, const int32_t *kill, const int32_t *moved, const double *msite,
+                      int nq, int mode, double *dist, double *value, int32_t *proven, int32_t *pos, int64_t info[4]);
+/* The DEVICE engine's bucket grid (csrc/chain_dev.h bucket_count / buckets / bslot) against its cell arrays,
+ * all copied back.  out[0] live slots found in no bucket, [1] live slots found in more than one, [2] entries
+ * whose (x, y, z, zeta) differ bitwise from cx / cy / cz / czeta[slot], [3] entries in a bucket other than
+ * grid_bucket(site), [4] entries that name a free slot or a slot >= nslots (plus buckets whose count is
+ * outside 0 .. 32), [5] the overflow flag, [6] the largest bucket count, [7] nslots.  [0..4] are 0 while the
+ * flag is clear; once it is set (a bucket was full: the chain scans every slot from then on) cells may be
+ * missing from the grid, so [0] alone may be non-zero.  Needs a GPU. */
+int tdt_chain_grid_check(td_chain *ch, int64_t out[8]);
+/* The cross-lane primitives of csrc/wave_ops.h, one wave per row: row r of in[nrows][64] holds lane l's 64-bit
+ * word at [r][l]; out[r][l] = what lane l gets back.  op 0 wave_min_u64, 1 wave_min_u64_2p, 2 wave_min_u32 of
+ * the low words (zero-extended), 3 wave_xor_u64, 4 row_max_u64 (specified in lanes 15, 31, 47, 63 only),
+ * 5 wave_scan_f64, 6 wave_sum_f64, 7 readlane_f64 of lane arg[r] (5..7: the words are doubles' bits).  arg is
+ * read for op 7 only: TD_ERR_ARG before any HIP call unless every arg[r] is in 0 .. 63.  1 <= nrows <= 65536.
+ * Needs a GPU. */
+int tdt_wave_ops(int device, int op, const uint64_t *in, const int32_t *arg, int64_t nrows, uint64_t *out);
+/* The chain's exact scan of every slot (csrc/chain_search.h wave_full_scan) on caller-given slot arrays
+ * (stamp[cap]: < 0 = a free slot; cx, cy, cz, czeta[cap]), one wave answering nq queries q[nq][3] one after
+ * another: the lexicographic minimum of (squared distance, stamp) over the slots s < nslots with stamp[s] >= 0
+ * and s != skip[i], slot moved[i] taken at msite[i][0..2] (-1: none of either); a cell wins only below the 1e9
+ * sentinel, else the answer is (1e9, -1, 0.0).  TD_ERR_ARG before any HIP call if nslots > cap or a skip /
+ * moved lies outside [-1, cap).  Needs a GPU. */
+int tdt_nearest_scan(int device, const int64_t *stamp, const double *cx, const double *cy, const double *cz,
+                     const double *czeta, int64_t cap, int64_t nslots, const double *q, const int32_t *skip,
+                     const int32_t *moved, const double *msite, int64_t nq, double *out_d, int32_t *out_slot,
+                     double *out_z);
 /* Metropolis-Hastings decision, eqs. 14-17 (:96-97, :151-152, :196, :241). */
 int tdt_accept(const td_chain_params *prm, int action, double u_accept, double zeta_new, int64_t ncells, double phi,
                double phi_n, double czeta, double zeta_killed, double zetanew_death);
@@ -174,6 +208,8 @@ int tdt_exact_sum(int device, const double *term, int64_t cnt, double C0, double
 /* The one-wave exact sequential sum (exact_sum.h wave_seq_sum, the chain's
  * chi^2 tail): same contract as tdt_exact_sum, always exact; *fallbacks =
  * 256-term chunks that needed the slower binade-by-binade path.  Needs a GPU. */
+int tdt_wave_seq_sum(int device, const double *term, int64_t cnt, double C0, double *prefix, double *C_end,
+                     int *fallbacks);
 /* The one-wave sum after a few terms changed (exact_sum.h wave_delta_sum, the
  * chain's chi^2): prefix[k] = C0 + term[0] + ... + term[k] left to right,
  * given old_prefix (the same sums over the old terms) and changed[k] != 0
@@ -190,8 +226,6 @@ int tdt_wave_delta_sum(int device, const double *term, const double *old_prefix,
 int tdt_block_delta_sum(int device, const double *term, const double *term_old, const double *old_prefix,
                         const int *changed, int64_t k0, int64_t n, double *prefix, double *C_end, int64_t *events,
                         int *mask_ok);
-int tdt_wave_seq_sum(int device, const double *term, int64_t cnt, double C0, double *prefix, double *C_end,
-                     int *fallbacks);
 
 /* chi^2 (MCsub.jl:169-172) of a caller-given ptS[n] against the context's tS
  * and allSig, through the code that computes it in the product: path 0

@@ -25,6 +25,7 @@ _pd = ctypes.POINTER(ctypes.c_double)
 _pi32 = ctypes.POINTER(ctypes.c_int32)
 _pi64 = ctypes.POINTER(ctypes.c_int64)
 _pu32 = ctypes.POINTER(ctypes.c_uint32)
+_pu64 = ctypes.POINTER(ctypes.c_uint64)
 _vp = ctypes.c_void_p
 
 
@@ -286,6 +287,12 @@ SIGNATURES = {
     "tdt_history_pack_chunk": (ctypes.c_int, []),
     "tdt_chain_query_lat": (ctypes.c_int, [_vp, _pd, ctypes.c_int, ctypes.c_int, _pi64]),
     "tdt_chain_query_answers": (ctypes.c_int, [_vp, _pd, ctypes.c_int, ctypes.c_int, _pd, _pd, _pi32]),
+    "tdt_chain_nearest": (ctypes.c_int, [_vp, _pd, _pi32, _pi32, _pd, ctypes.c_int, ctypes.c_int, _pd, _pd, _pi32, _pi32,
+                                         _pi64]),
+    "tdt_chain_grid_check": (ctypes.c_int, [_vp, _pi64]),
+    "tdt_wave_ops": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _pu64, _pi32, _i64, _pu64]),
+    "tdt_nearest_scan": (ctypes.c_int, [ctypes.c_int, _pi64, _pd, _pd, _pd, _pd, _i64, _i64, _pd, _pi32, _pi32, _pd,
+                                        _i64, _pd, _pi32, _pd]),
     "tdt_tile_filter": (ctypes.c_int, [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _pd,
                                        ctypes.c_int, _pd, ctypes.c_int, ctypes.c_int,
                                        ctypes.POINTER(ctypes.c_uint8)]),
@@ -357,7 +364,7 @@ def f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
-_ARRAY_PTRS = (_pd, _pi32, _pi64, _pu32)
+_ARRAY_PTRS = (_pd, _pi32, _pi64, _pu32, _pu64)
 
 
 def ptr(a, t=_pd):

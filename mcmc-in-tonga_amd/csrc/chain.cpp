@@ -2199,6 +2199,193 @@ int tdt_chain_query_answers(td_chain *ch, const double *pts, int nq, int mode, d
     return TD_OK;
 }
 
+int tdt_chain_nearest(td_chain *ch, const double *pts, const int32_t *kill, const int32_t *moved, const double *msite,
+                      int nq, int mode, double *dist, double *value, int32_t *proven, int32_t *pos, int64_t info[4]) {
+    if (!ch || ch->engine != TD_ENGINE_DEVICE || !pts || !kill || !moved || !msite || nq < 1 || !dist || !value ||
+        !proven || !pos || !info || (mode != 0 && mode != 6 && mode != 7))
+        return TD_ERR_ARG;
+    td_ctx *c = ch->ctx;
+    const DevChain &d = ch->dev;
+    ChainScalars st{};
+    int ovf = 0;
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(&st, ch->st_dev, sizeof st, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&ovf, d.grid_overflow, sizeof ovf, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_err(c, e, "tdt_chain_nearest");
+    if (st.ncells < 0 || st.ncells > d.cap || st.nslots < st.ncells || st.nslots > d.cap)
+        return set_err(c, TD_ERR_LAYOUT, "tdt_chain_nearest: the chain's cell counts are out of range");
+    for (int i = 0; i < nq; ++i)  // (the kernel indexes d.order with them)
+        if (kill[i] < -1 || kill[i] >= st.ncells || moved[i] < -1 || moved[i] >= st.ncells) return TD_ERR_ARG;
+    std::vector<int> order((size_t)st.ncells), inv((size_t)d.cap, -1), slot((size_t)nq);
+    if (!order.empty()) e = hipMemcpy(order.data(), d.order, sizeof(int) * order.size(), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_err(c, e, "tdt_chain_nearest");
+    for (int p = 0; p < st.ncells; ++p) {
+        const int s = order[(size_t)p];
+        if (s < 0 || s >= st.nslots) return set_err(c, TD_ERR_LAYOUT, "tdt_chain_nearest: order names no slot");
+        inv[(size_t)s] = p;
+    }
+    double *dp = nullptr, *dm = nullptr, *dd = nullptr, *dz = nullptr;
+    int *dk = nullptr, *dv = nullptr, *dpr = nullptr, *ds = nullptr;
+    const size_t n = (size_t)nq;
+    e = hipMalloc((void **)&dp, sizeof(double) * 3 * n);
+    if (e == hipSuccess) e = hipMalloc((void **)&dm, sizeof(double) * 3 * n);
+    if (e == hipSuccess) e = hipMalloc((void **)&dd, sizeof(double) * n);
+    if (e == hipSuccess) e = hipMalloc((void **)&dz, sizeof(double) * n);
+    if (e == hipSuccess) e = hipMalloc((void **)&dk, sizeof(int) * n);
+    if (e == hipSuccess) e = hipMalloc((void **)&dv, sizeof(int) * n);
+    if (e == hipSuccess) e = hipMalloc((void **)&dpr, sizeof(int) * n);
+    if (e == hipSuccess) e = hipMalloc((void **)&ds, sizeof(int) * n);
+    if (e == hipSuccess) e = hipMemcpy(dp, pts, sizeof(double) * 3 * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dm, msite, sizeof(double) * 3 * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dk, kill, sizeof(int) * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dv, moved, sizeof(int) * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess && ch->desc_dirty) {
+        e = hipMemcpy(ch->dev_ptr, &ch->dev, sizeof(DevChain), hipMemcpyHostToDevice);
+        ch->desc_dirty = false;
+    }
+    if (e == hipSuccess) e = test_chain_nearest(ch->dev_ptr, dp, dk, dv, dm, nq, mode, dd, dz, dpr, ds, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(dist, dd, sizeof(double) * n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(value, dz, sizeof(double) * n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(proven, dpr, sizeof(int) * n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(slot.data(), ds, sizeof(int) * n, hipMemcpyDeviceToHost);
+    for (void *q : {(void *)dp, (void *)dm, (void *)dd, (void *)dz, (void *)dk, (void *)dv, (void *)dpr, (void *)ds})
+        if (q) (void)hipFree(q);
+    if (e != hipSuccess) return hip_err(c, e, "tdt_chain_nearest");
+    for (size_t i = 0; i < n; ++i) {  // the winner's slot as its Julia position (-2: a slot no position names)
+        const int s = slot[i];
+        pos[i] = s < 0 ? -1 : (s < d.cap && inv[(size_t)s] >= 0 ? inv[(size_t)s] : -2);
+    }
+    info[0] = st.nslots;
+    info[1] = d.cap;
+    info[2] = st.ncells;
+    info[3] = ovf;
+    return TD_OK;
+}
+
+// The bucket grid against the cell arrays (all copied back): every live slot in exactly one bucket, at
+// grid_bucket(its site), its entry bit-equal to the cell arrays
+int tdt_chain_grid_check(td_chain *ch, int64_t out[8]) {
+    if (!ch || ch->engine != TD_ENGINE_DEVICE || !out) return TD_ERR_ARG;
+    td_ctx *c = ch->ctx;
+    const DevChain &d = ch->dev;
+    const size_t nb = (size_t)d.grid.gx * d.grid.gy * d.grid.gz, cap = (size_t)d.cap;
+    std::vector<int> bcount(nb), bslot(nb * kBucketCap);
+    std::vector<CellEntry> bent(nb * kBucketCap);
+    std::vector<long long> stamp(cap);
+    std::vector<double> cells(4 * cap);
+    ChainScalars st{};
+    int ovf = 0;
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(&st, ch->st_dev, sizeof st, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&ovf, d.grid_overflow, sizeof ovf, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(bcount.data(), d.bucket_count, sizeof(int) * nb, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(bslot.data(), d.bslot, sizeof(int) * bslot.size(), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(bent.data(), d.buckets, sizeof(CellEntry) * bent.size(), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(stamp.data(), d.stamp, sizeof(long long) * cap, hipMemcpyDeviceToHost);
+    const double *src[4] = {d.cx, d.cy, d.cz, d.czeta};
+    for (size_t a = 0; a < 4 && e == hipSuccess; ++a)
+        e = hipMemcpy(cells.data() + a * cap, src[a], sizeof(double) * cap, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_err(c, e, "tdt_chain_grid_check");
+    const double *cx = cells.data(), *cy = cx + cap, *cz = cy + cap, *cv = cz + cap;
+    const int nslots = st.nslots;
+    std::vector<int> seen(cap, 0);
+    int64_t differ = 0, misplaced = 0, badslot = 0, maxcount = 0;
+    for (size_t b = 0; b < nb; ++b) {
+        const int cnt = bcount[b];
+        maxcount = std::max<int64_t>(maxcount, cnt);
+        if (cnt < 0 || cnt > kBucketCap) badslot += 1;  // (a count no bucket can hold)
+        for (int k = 0; k < std::min(std::max(cnt, 0), kBucketCap); ++k) {
+            const int s = bslot[b * kBucketCap + (size_t)k];
+            if (s < 0 || s >= nslots || (size_t)s >= cap || stamp[(size_t)s] < 0) {
+                badslot += 1;
+                continue;
+            }
+            seen[(size_t)s] += 1;
+            const CellEntry &en = bent[b * kBucketCap + (size_t)k];
+            const double have[4] = {en.x, en.y, en.z, en.zeta};
+            const double want[4] = {cx[s], cy[s], cz[s], cv[s]};
+            differ += std::memcmp(have, want, sizeof have) != 0;
+            misplaced += (size_t)grid_bucket(d.grid, cx[s], cy[s], cz[s]) != b;
+        }
+    }
+    int64_t none = 0, many = 0;
+    for (int s = 0; s < nslots && (size_t)s < cap; ++s) {
+        if (stamp[(size_t)s] < 0) continue;
+        none += seen[(size_t)s] == 0;
+        many += seen[(size_t)s] > 1;
+    }
+    out[0] = none;
+    out[1] = many;
+    out[2] = differ;
+    out[3] = misplaced;
+    out[4] = badslot;
+    out[5] = ovf;
+    out[6] = maxcount;
+    out[7] = nslots;
+    return TD_OK;
+}
+
+int tdt_wave_ops(int device, int op, const uint64_t *in, const int32_t *arg, int64_t nrows, uint64_t *out) {
+    if (!in || !out || op < 0 || op > 7 || nrows < 1 || nrows > 65536 || (op == 7 && !arg)) return TD_ERR_ARG;
+    if (op == 7)
+        for (int64_t r = 0; r < nrows; ++r)
+            if (arg[r] < 0 || arg[r] > 63) return TD_ERR_ARG;
+    if (hipSetDevice(device) != hipSuccess) return TD_ERR_HIP;
+    const size_t nbytes = sizeof(uint64_t) * 64 * (size_t)nrows;
+    void *buf = nullptr;
+    if (hipMalloc(&buf, 2 * nbytes + sizeof(int) * (size_t)nrows) != hipSuccess) return TD_ERR_NOMEM;
+    unsigned long long *din = static_cast<unsigned long long *>(buf), *dout = din + 64 * nrows;
+    int *darg = reinterpret_cast<int *>(dout + 64 * nrows);
+    hipError_t e = hipMemcpy(din, in, nbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && op == 7) e = hipMemcpy(darg, arg, sizeof(int) * (size_t)nrows, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(dout, 0, nbytes);
+    if (e == hipSuccess) e = test_wave_ops(din, darg, (int)nrows, op, dout, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, dout, nbytes, hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    return e == hipSuccess ? TD_OK : TD_ERR_HIP;
+}
+
+int tdt_nearest_scan(int device, const int64_t *stamp, const double *cx, const double *cy, const double *cz,
+                     const double *czeta, int64_t cap, int64_t nslots, const double *q, const int32_t *skip,
+                     const int32_t *moved, const double *msite, int64_t nq, double *out_d, int32_t *out_slot,
+                     double *out_z) {
+    if (!stamp || !cx || !cy || !cz || !czeta || !q || !skip || !moved || !msite || !out_d || !out_slot || !out_z ||
+        cap < 1 || cap > (1 << 24) || nslots < 0 || nslots > cap || nq < 1 || nq > (1 << 20))
+        return TD_ERR_ARG;
+    for (int64_t i = 0; i < nq; ++i)
+        if (skip[i] < -1 || skip[i] >= cap || moved[i] < -1 || moved[i] >= cap) return TD_ERR_ARG;
+    if (hipSetDevice(device) != hipSuccess) return TD_ERR_HIP;
+    const size_t C = (size_t)cap, Q = (size_t)nq;
+    // one block: the 8-byte arrays first (stamp, 4 cell arrays, q, msite, out_d, out_z), then the ints
+    const size_t n8 = 5 * C + 8 * Q, n4 = 3 * Q;
+    void *buf = nullptr;
+    if (hipMalloc(&buf, 8 * n8 + 4 * n4) != hipSuccess) return TD_ERR_NOMEM;
+    long long *dst = static_cast<long long *>(buf);
+    double *dx = reinterpret_cast<double *>(dst + C), *dy = dx + C, *dz = dy + C, *dv = dz + C;
+    double *dq = dv + C, *dm = dq + 3 * Q, *dod = dm + 3 * Q, *doz = dod + Q;
+    int *dsk = reinterpret_cast<int *>(doz + Q), *dmv = dsk + Q, *dos = dmv + Q;
+    hipError_t e = hipMemcpy(dst, stamp, 8 * C, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dx, cx, 8 * C, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dy, cy, 8 * C, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dz, cz, 8 * C, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dv, czeta, 8 * C, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dq, q, 8 * 3 * Q, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dm, msite, 8 * 3 * Q, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dsk, skip, 4 * Q, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dmv, moved, 4 * Q, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = test_nearest_scan(dst, dx, dy, dz, dv, (int)cap, (int)nslots, dq, dsk, dmv, dm, (int)nq, dod, dos, doz,
+                              nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out_d, dod, 8 * Q, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_z, doz, 8 * Q, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_slot, dos, 4 * Q, hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    return e == hipSuccess ? TD_OK : TD_ERR_HIP;
+}
+
 int tdt_chain_profile(td_chain *ch, int enable, int64_t out[80]) {
     if (!ch || ch->engine != TD_ENGINE_DEVICE) return TD_ERR_ARG;
     ch->dev.profile = enable;

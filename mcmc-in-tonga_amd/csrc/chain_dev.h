@@ -371,6 +371,19 @@ hipError_t test_tile_filter(const float *lo, const float *hi, const double *maxd
                             int mode, unsigned char *out, hipStream_t s);
 hipError_t test_query_answers(const DevChain *dev, const double *pts, int nq, int mode, double *out_d, double *out_z,
                               int *out_p, hipStream_t s);
+// Testing: wave_ops.h's primitive `op` on each row of in[nrows][64], one wave per row (k_test_wave_ops)
+hipError_t test_wave_ops(const unsigned long long *in, const int *arg, int nrows, int op, unsigned long long *out,
+                         hipStream_t s);
+// Testing: wave_full_scan on caller-given slot arrays, one wave, query after query (k_test_nearest_scan)
+hipError_t test_nearest_scan(const long long *stamp, const double *cx, const double *cy, const double *cz,
+                             const double *czeta, int cap, int nslots, const double *q, const int *skip,
+                             const int *moved, const double *msite, int nq, double *out_d, int *out_s, double *out_z,
+                             hipStream_t s);
+// Testing: the chain's nearest-cell query with a killed and a moved cell (Julia positions), mode 0 / 6 the two
+// grid searches, 7 wave_nearest; out_s = the winner's slot (k_test_chain_nearest)
+hipError_t test_chain_nearest(const DevChain *dev, const double *pts, const int *kill_pos, const int *move_pos,
+                              const double *msite, int nq, int mode, double *out_d, double *out_z, int *out_p,
+                              int *out_s, hipStream_t s);
 // LDS bytes of the two layouts, whether super-tiles fit, and the layout chain_run takes.
 void chain_lds_sizes(const DevChain &d, int64_t out[4]);
 

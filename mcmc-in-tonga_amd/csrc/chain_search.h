@@ -1,7 +1,11 @@
 // chain_search.h -- a chain's nearest-cell search (one wave per query): the exact scan of every slot,
 // the search through the bucket grid's LDS copy, the two together (wave_nearest), and the grid's
 // update for an accepted proposal (grid_prefetch / grid_apply).  The search that reads the grid's
-// descriptor (DevChain) instead is the comparison form in chain_test_kernels.hip.
+// descriptor (DevChain) instead is the comparison form in chain_test_kernels.hip, kept for the tests:
+// test_grid_query_forms_agree (no edit) and test_gpu_nearest_edits.py (a killed and a moved cell; the grid
+// against the cell arrays after every kind of update) hold the two searches together and to an exact scan;
+// test_gpu_nearest_scan.py holds wave_full_scan to built slot layouts, test_gpu_wave_ops.py the reductions
+// under all of them.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,7 @@
 // chain_test_kernels.hip -- testing kernels for pieces of the device chain (tdstar_testing.h hooks; the
 // product never launches them): phase F's proposal-time chi^2, the grid query's latency and answers,
-// the phase-B tile filters.
+// the phase-B tile filters, the wave primitives of wave_ops.h row by row, the full scan on caller-given
+// slots, and a chain's nearest-cell query with a killed and a moved cell.
 #pragma clang fp contract(off)
 // (a unit uses part of what the chain_*.h headers define, each with internal linkage)
 #pragma clang diagnostic ignored "-Wunused-function"
@@ -281,6 +282,122 @@ hipError_t test_query_answers(const DevChain *dev, const double *pts, int nq, in
 
 hipError_t test_query_lat(const DevChain *dev, const double *pts, int nq, int mode, long long *out, hipStream_t s) {
     hipLaunchKernelGGL(k_test_query_lat, dim3(1), dim3(64), 0, s, dev, pts, nq, mode, out);
+    return hipGetLastError();
+}
+
+namespace {
+
+// Testing: the cross-lane primitives of wave_ops.h, one wave per block: block r applies primitive `op` to
+// row r of in[nrows][64] (lane l holds word l) and writes every lane's result to out[nrows][64]
+// (tdt_wave_ops).  op 0 wave_min_u64, 1 wave_min_u64_2p, 2 wave_min_u32 on the low words, 3 wave_xor_u64,
+// 4 row_max_u64, 5 wave_scan_f64, 6 wave_sum_f64, 7 readlane_f64 of lane arg[r] (the host has checked
+// 0 <= arg[r] < 64; one row's lane is wave-uniform).
+__global__ __launch_bounds__(64) void k_test_wave_ops(const unsigned long long *__restrict__ in,
+                                                       const int *__restrict__ arg, int op,
+                                                       unsigned long long *__restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    const unsigned long long v = in[i];
+    const double f = __longlong_as_double((long long)v);
+    unsigned long long r = 0ull;
+    switch (op) {
+        case 0: r = wave_min_u64(v); break;
+        case 1: r = wave_min_u64_2p(v); break;
+        case 2: r = (unsigned long long)wave_min_u32((unsigned)v); break;
+        case 3: r = wave_xor_u64(v); break;
+        case 4: r = row_max_u64(v); break;
+        case 5: r = (unsigned long long)__double_as_longlong(wave_scan_f64(f)); break;
+        case 6: r = (unsigned long long)__double_as_longlong(wave_sum_f64(f)); break;
+        default: r = (unsigned long long)__double_as_longlong(readlane_f64(f, arg[blockIdx.x])); break;
+    }
+    out[i] = r;
+}
+
+// Testing: wave_full_scan on caller-given slot arrays, one wave answering the queries one after another
+// (tdt_nearest_scan).  The host has checked 1 <= cap, 0 <= nslots <= cap and every skip / moved in
+// [-1, cap): the scan reads slots min(s, cap - 1) only, and the winner is a slot below nslots.
+__global__ __launch_bounds__(64) void k_test_nearest_scan(
+    const long long *__restrict__ stamp, const double *__restrict__ cx, const double *__restrict__ cy,
+    const double *__restrict__ cz, const double *__restrict__ czeta, int cap, int nslots,
+    const double *__restrict__ q, const int *__restrict__ skip, const int *__restrict__ moved,
+    const double *__restrict__ msite, int nq, double *out_d, int *out_s, double *out_z) {
+    const int lane = threadIdx.x;
+    for (int i = 0; i < nq; ++i) {
+        const Nearest r = wave_full_scan(stamp, cx, cy, cz, czeta, cap, nslots, lane, q[3 * i], q[3 * i + 1],
+                                         q[3 * i + 2], skip[i], moved[i], msite[3 * i], msite[3 * i + 1],
+                                         msite[3 * i + 2]);
+        if (lane == 0) {
+            out_d[i] = r.d;
+            out_s[i] = r.s;
+            out_z[i] = r.z;
+        }
+    }
+}
+
+// Testing: a chain's nearest-cell query with a killed and a moved cell, as phases B and D and the drop-in
+// query ask it (tdt_chain_nearest): per query a killed and a moved cell as 0-based Julia positions (-1:
+// none; the host has checked them against ncells), mapped to slots through d.order as k_chain_run maps
+// them, the moved cell's site, and czeta[moved] as its value.  mode 0: the product's wave_grid_search on
+// the LDS GridGeo, 6: the descriptor form above, 7: wave_nearest (grid, then the full scan).  One wave;
+// out_s = the winner's slot (-1: none).
+__global__ __launch_bounds__(64) void k_test_chain_nearest(const DevChain *__restrict__ dptr,
+                                                           const double *__restrict__ pts,
+                                                           const int *__restrict__ kill_pos,
+                                                           const int *__restrict__ move_pos,
+                                                           const double *__restrict__ msite, int nq, int mode,
+                                                           double *out_d, double *out_z, int *out_p, int *out_s) {
+    __shared__ Shared sh;
+    const DevChain &d = *dptr;
+    const int lane = threadIdx.x;
+    Views v{};
+    v.ord = d.order;
+    if (lane == 0) {
+        sh.grid_ovf = *d.grid_overflow;
+        sh.grid_fallbacks32 = 0;
+        sh.nslots = d.st->nslots;
+        geo_fill(sh.geo, d);
+    }
+    __syncthreads();
+    for (int i = 0; i < nq; ++i) {
+        const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
+        const int skip = kill_pos[i] >= 0 ? d.order[kill_pos[i]] : -1;
+        const int moved = move_pos[i] >= 0 ? d.order[move_pos[i]] : -1;
+        const double mx = msite[3 * i], my = msite[3 * i + 1], mz = msite[3 * i + 2];
+        const double mzeta = moved >= 0 ? d.czeta[moved] : 0.0;
+        Nearest r;
+        if (mode == 0) r = wave_grid_search(sh.geo, sh.grid_ovf != 0, lane, x, y, z, skip, moved, mx, my, mz, mzeta);
+        else if (mode == 6) r = wave_grid_search(d, sh.grid_ovf != 0, lane, x, y, z, skip, moved, mx, my, mz, mzeta);
+        else r = wave_nearest(d, v, sh, lane, x, y, z, skip, moved, mx, my, mz, mzeta);
+        if (lane == 0) {
+            out_d[i] = r.d;
+            out_z[i] = r.z;
+            out_p[i] = r.proven ? 1 : 0;
+            out_s[i] = r.s;
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t test_wave_ops(const unsigned long long *in, const int *arg, int nrows, int op, unsigned long long *out,
+                         hipStream_t s) {
+    hipLaunchKernelGGL(k_test_wave_ops, dim3((unsigned)nrows), dim3(64), 0, s, in, arg, op, out);
+    return hipGetLastError();
+}
+
+hipError_t test_nearest_scan(const long long *stamp, const double *cx, const double *cy, const double *cz,
+                             const double *czeta, int cap, int nslots, const double *q, const int *skip,
+                             const int *moved, const double *msite, int nq, double *out_d, int *out_s, double *out_z,
+                             hipStream_t s) {
+    hipLaunchKernelGGL(k_test_nearest_scan, dim3(1), dim3(64), 0, s, stamp, cx, cy, cz, czeta, cap, nslots, q, skip,
+                       moved, msite, nq, out_d, out_s, out_z);
+    return hipGetLastError();
+}
+
+hipError_t test_chain_nearest(const DevChain *dev, const double *pts, const int *kill_pos, const int *move_pos,
+                              const double *msite, int nq, int mode, double *out_d, double *out_z, int *out_p,
+                              int *out_s, hipStream_t s) {
+    hipLaunchKernelGGL(k_test_chain_nearest, dim3(1), dim3(64), 0, s, dev, pts, kill_pos, move_pos, msite, nq, mode,
+                       out_d, out_z, out_p, out_s);
     return hipGetLastError();
 }
 
