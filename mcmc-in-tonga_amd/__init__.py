@@ -21,9 +21,9 @@ from .defstruct import DataStruct, Model, Ray  # noqa: F401
 from .forward import Interpolation, TdContext, context_for, evaluate, v_nearest  # noqa: F401
 from .tempering import Exchange, NativeComm, TemperingLadder, decide_swaps, geometric_ladder  # noqa: F401
 from .posterior import (box_region, checkerboard_model, compare_summary, convergence_maps, credible_maps,  # noqa: F401
-                        depth_layers, info_gain_bits, model_distributions, plot_model_hist, posterior_compare,
-                        posterior_covariance, posterior_interfaces,
-                        posterior_predictive, posterior_recovery, posterior_regions, posterior_resolution,
+                        depth_layers, distance_summary, ensemble_distances, info_gain_bits, model_distributions,
+                        pattern_summary, plot_model_hist, posterior_compare, posterior_covariance, posterior_interfaces,
+                        posterior_patterns, posterior_predictive, posterior_recovery, posterior_regions, posterior_resolution,
                         posterior_support, posterior_volume, ray_density, region_points, resolution_offsets, section,
                         support_weights, synthetic_data, trace_diagnostics, voxel_weights)
 from .sharded import RayShardedContext, ray_points, shard_rays, sub_datastruct  # noqa: F401

@@ -183,6 +183,24 @@ SIGNATURES_COMPARE = {
     "tdt_set_compare_form": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
 }
 
+
+class TdGram(ctypes.Structure):
+    """td_gram (include/tdstar_gram.h); the arrays as plain addresses (ptr())."""
+    _fields_ = [("px", _vp), ("py", _vp), ("pz", _vp), ("w", _vp), ("np", _i64), ("gram_out", _vp), ("dist2_out", _vp),
+                ("mean_out", _vp), ("std_out", _vp), ("wsum_out", _vp)]
+
+
+# name -> (restype, argtypes); every symbol declared in include/tdstar_gram.h, which tdstar.h does not include
+# (applied by lib() as SIGNATURES is)
+SIGNATURES_GRAM = {
+    "td_rasterize_gram": (ctypes.c_int, [_vp, _i64, _pi64, _pd, _pd, _pd, _pd, ctypes.POINTER(TdGram)]),
+    "td_history_gram": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), _i64, ctypes.POINTER(TdGram)]),
+    "tdt_gram_plan": (ctypes.c_int, [_i64, _i64, _i64, _i64, _pi64]),
+    "tdt_set_gram_form": (ctypes.c_int, [ctypes.c_int]),
+    "tdt_gram_tile": (ctypes.c_int, [ctypes.c_int]),
+    "tdt_gram_tiles": (_i64, [_i64, ctypes.c_int, _i64, _pi64]),
+}
+
 # name -> (restype, argtypes); every symbol declared in include/tdstar.h and include/tdstar_testing.h
 SIGNATURES = {
     "td_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _pd, _pd, _pd, _pd, _pd, _i64, _i64, _pd, _pd]),
@@ -340,7 +358,7 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         older = "TD_LIB_PATH" in os.environ  # (an A/B against an older build: newer testing hooks may be absent)
         later = dict(SIGNATURES_INTERFACES, **SIGNATURES_REGIONS, **SIGNATURES_SUPPORT, **SIGNATURES_RECOVERY,
-                     **SIGNATURES_RESOLUTION, **SIGNATURES_COMPARE)  # (the headers of their own)
+                     **SIGNATURES_RESOLUTION, **SIGNATURES_COMPARE, **SIGNATURES_GRAM)  # (the headers of their own)
         for name, (res, args) in list(SIGNATURES.items()) + list(later.items()):
             if older and (name.startswith("tdt_") or name in later) and not hasattr(L, name):
                 continue

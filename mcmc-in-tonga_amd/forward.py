@@ -727,6 +727,74 @@ class TdContext:
 
         return self._regions(call, nm, px, py, pz, reg_off, w, normalize, probs, bins, convergence, max_lag, greater)
 
+    GRAM_MAX_MODELS = 11585  # 8 M^2 bytes of a matrix within 1 GiB (include/tdstar_gram.h)
+
+    @staticmethod
+    def gram_plan(nmodels, npoints, budget=0, forced=0):
+        """(the points a slab sweeps, slabs) of a ``gram`` call on ``npoints`` points (budget in bytes, 0: 1 GiB):
+        ``volume_plan``'s numbers with the point list in the place of the nodes; needs no GPU."""
+        out = np.zeros(2, dtype=np.int64)
+        check(lib().tdt_gram_plan(int(nmodels), int(npoints), int(budget), int(forced), ptr(out, _lib._pi64)))
+        return int(out[0]), int(out[1])
+
+    @staticmethod
+    def set_gram_form(form=0):
+        """Testing hook, process-wide: the pair kernel's register tile (0: the kept one, 1: 4 x 4 pairs a lane, 2:
+        8 x 8); no answer depends on it."""
+        check(lib().tdt_set_gram_form(int(form)))
+
+    @staticmethod
+    def gram_tile(form=0):
+        """The rows of the tile of the lower triangle a workgroup of the pair kernel owns under ``form``; needs no GPU."""
+        return int(lib().tdt_gram_tile(int(form)))
+
+    def _gram(self, call, nmodels, px, py, pz, w, want):
+        """The td_gram request around ``call(byref(req))`` -> dict of the outputs."""
+        px, py, pz = (f64(np.ravel(a)) for a in (px, py, pz))
+        npts = len(px)
+        if not (len(py) == len(pz) == npts):
+            raise ValueError("px, py and pz must have the same length")
+        wv = f64(np.ravel(w)) if w is not None else None
+        if wv is not None and len(wv) != npts:
+            raise ValueError("w must have one weight per point")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not set(want) <= {"gram", "dist2"}:
+            raise ValueError("want: 'gram' and / or 'dist2'")
+        res = dict(gram=np.empty((nmodels, nmodels)) if "gram" in want else None,
+                   dist2=np.empty((nmodels, nmodels)) if "dist2" in want else None, mean=np.empty(npts), std=np.empty(npts),
+                   wsum=np.empty(1))
+        req = _lib.TdGram(ptr(px), ptr(py), ptr(pz), ptr(wv), npts, ptr(res["gram"]), ptr(res["dist2"]), ptr(res["mean"]),
+                          ptr(res["std"]), ptr(res["wsum"]))
+        call(ctypes.byref(req))
+        res["wsum"] = float(res["wsum"][0])
+        return res
+
+    def gram(self, models, px, py, pz, w=None, want=("gram", "dist2")):
+        """td_rasterize_gram: the M x M matrices of inner products and of squared distances between the models'
+        volumes on the points ``px``, ``py``, ``pz`` with the weights ``w`` >= 0 (None: 1.0).  With V[m][p] the
+        nearest-cell value of model m at point p (``volume``'s), mean[p] its mean over the models and X[m][p] =
+        sqrt(w[p]) * (V[m][p] - mean[p]) -> dict(gram[M, M] = sum_p X[a][p] X[b][p], dist2[M, M] = sum_p (X[a][p] -
+        X[b][p])^2 (each None unless in ``want``), mean[np], std[np] (``volume``'s), wsum = sum(w)).  Both sums run over
+        the points in order in blocks of 64 without FMA (include/tdstar_gram.h): the matrices are symmetric bit for bit
+        and depend on neither the slabs nor the kernel's tiling.  Any number of points, swept slab by slab as by
+        ``volume``; at most 11585 models (1 GiB a matrix).  models as for ``rasterize``."""
+        off, cat = _pack_models(models)
+
+        def call(req):
+            check(lib().td_rasterize_gram(self.h, len(models), ptr(off, _lib._pi64), *(ptr(c) for c in cat), req), self.h)
+
+        return self._gram(call, len(models), px, py, pz, w, want)
+
+    def gram_history(self, histories, px, py, pz, w=None, want=("gram", "dist2")):
+        """td_history_gram: ``gram`` on the samples of the histories (chain.History) where they lie, history by
+        history (one without samples is skipped); they may have been recorded on another context of this device."""
+        hs, nm = _history_handles(histories)
+
+        def call(req):
+            check(lib().td_history_gram(self.h, hs, len(hs), req), self.h)
+
+        return self._gram(call, nm, px, py, pz, w, want)
+
     def _recovery(self, call, nmodels, px, py, pz, truth, reg_off, w, normalize, probs, bins, conv, max_lag):
         """The td_recovery request around ``call(byref(req))`` -> dict of the outputs."""
         px, py, pz, tr = (f64(np.ravel(a)) for a in (px, py, pz, truth))

@@ -737,6 +737,157 @@ def posterior_compare(model_hist_a, model_hist_b, dataStruct, TD_parameters, exc
     return out
 
 
+def _node_weights(weights, xv, yv, zv, shape):
+    """``weights`` of the ensemble calls on a lattice as the device reads them (x fastest), or None: "volume" ->
+    ``voxel_weights``; None; an array [nx, ny, nz]."""
+    if isinstance(weights, str):
+        if weights != "volume":
+            raise ValueError("weights: 'volume', None or an array [nx, ny, nz]")
+        weights = voxel_weights(xv, yv, zv)
+    if weights is None:
+        return None
+    w = np.asarray(weights, dtype=np.float64)
+    if w.shape != shape[::-1]:
+        raise ValueError("weights must be [nx, ny, nz] = %s; got %s" % (shape[::-1], w.shape))
+    return w.transpose(2, 1, 0).ravel()
+
+
+def _thinned(model_hist, thin):
+    """``_chains`` with every ``thin``-th sample of each chain kept (the first one included).  Histories are swept
+    where they lie and cannot be read with a stride: ``thin`` > 1 is refused for them."""
+    thin = int(thin)
+    if thin < 1:
+        raise ValueError("thin must be >= 1")
+    models, lens = _chains(model_hist)
+    if thin == 1:
+        return models, lens
+    if _on_device(models):
+        raise ValueError("thin > 1 on device histories: a History is swept where it lies, every sample of it; record "
+                         "thinner (keep_each, or run_recorded's `every`) or pass the Models read back")
+    kept, klens, pos = [], [], 0
+    for n in lens:
+        part = models[pos:pos + n:thin]
+        kept += part
+        klens.append(len(part))
+        pos += n
+    return kept, klens
+
+
+def distance_summary(dist2, wsum, lens):
+    """``ensemble_distances``' numbers from the matrix of squared distances dist2 [M, M], the weights' sum and the
+    chains' lengths (pure numpy).  -> dict: ``dist`` = sqrt(dist2 / wsum); ``row_mean`` [M], a sample's mean distance
+    to the OTHER samples (0 for a single sample); ``medoid``, the argmin of the row sums of dist, the first index on
+    ties (a row whose sum is NaN never wins); ``chain_of`` [M]; ``chain_distance`` [C, C], the mean of dist over a in
+    chain c and b in chain d with a != b (NaN within a chain of one sample)."""
+    d2 = np.asarray(dist2, dtype=np.float64)
+    M = len(d2)
+    lens = [int(n) for n in lens]
+    if sum(lens) != M:
+        raise ValueError("the chains' lengths must sum to the samples (%d); got %s" % (M, lens))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        dist = np.sqrt(d2 / np.float64(wsum))
+    rows = dist.sum(axis=1)
+    medoid = int(np.argmin(np.where(np.isnan(rows), np.inf, rows)))
+    chain_of = np.repeat(np.arange(len(lens)), lens)
+    edges = np.concatenate(([0], np.cumsum(lens)))
+    C = len(lens)
+    cd = np.full((C, C), np.nan)
+    for c in range(C):
+        for d in range(C):
+            blk = dist[edges[c]:edges[c + 1], edges[d]:edges[d + 1]]
+            if c != d:
+                pairs, total = blk.size, blk.sum()
+            else:
+                pairs, total = blk.size - len(blk), blk.sum() - np.trace(blk)
+            if pairs > 0:
+                cd[c, d] = total / pairs
+    return {"dist": dist, "medoid": medoid, "row_mean": rows / (M - 1) if M > 1 else np.zeros(M), "chain_of": chain_of,
+            "chain_distance": cd}
+
+
+def ensemble_distances(model_hist, dataStruct, TD_parameters, weights="volume", thin=1, xs=None, ys=None, zs=None):
+    """Which sample represents the ensemble, and do the chains sample the same part of model space?  The mean of
+    Voronoi models is not a Voronoi model: what can be published is a member, the medoid.  On the lattice ``xs`` x
+    ``ys`` x ``zs`` (default: dataStruct.xVec / yVec / zVec) with a node's weight its voxel's volume
+    (``weights="volume"``; None: every node 1; or an array [nx, ny, nz] >= 0) -> dict: ``dist`` [M, M], the RMS
+    difference of two samples' volumes in zeta units, sqrt(dist2 / sum(w)); ``medoid``, the index of the sample with
+    the smallest summed distance to the others (the first on ties); ``row_mean`` [M]; ``chain_distance`` [C, C], the
+    mean distance between samples of chain c and chain d (a != b) -- chains that mix have off-diagonal entries like
+    the diagonal's; ``chain_of`` [M]; ``weight_sum``; ``mean``, ``std`` [nx, ny, nz] (``posterior_volume``'s).
+    ``thin`` keeps every thin-th sample of each chain (Model lists only; histories are swept whole).  Same inputs as
+    ``posterior_volume``; the M x M matrix is formed on the device slab by slab (td_rasterize_gram / td_history_gram)
+    and M is at most 11585."""
+    ctx = context_for(dataStruct)  # (TD_parameters: the siblings' signature; the lattice decides everything here)
+    xv, yv, zv, shape, qx, qy, qz = _lattice(dataStruct, xs, ys, zs)
+    w = _node_weights(weights, xv, yv, zv, shape)
+    models, lens = _thinned(model_hist, thin)
+    if _on_device(models):
+        r = ctx.gram_history(models, qx, qy, qz, w, want=("dist2",))
+    else:
+        r = ctx.gram([m.cells() for m in models], qx, qy, qz, w, want=("dist2",))
+    out = distance_summary(r["dist2"], r["wsum"], lens)
+    out.update(weight_sum=r["wsum"], x=xv, y=yv, z=zv, mean=_grid(r["mean"], shape), std=_grid(r["std"], shape))
+    return out
+
+
+def pattern_summary(gram, k=8):
+    """``posterior_patterns``' eigen step on the Gram matrix [M, M] of the centred samples (pure numpy,
+    numpy.linalg.eigh).  -> dict: ``eigenvalues`` [k] (the largest first, k at most M), ``vectors`` [M, k] with each
+    eigenvector's component of largest magnitude positive (the first such index on ties), ``scores`` [M, k] = vectors
+    * sqrt(max(eigenvalue, 0)), ``explained`` = eigenvalues / trace(gram), ``participation`` = (sum lambda)^2 / sum
+    lambda^2 over all M eigenvalues: the number of patterns that carry the variance."""
+    G = np.asarray(gram, dtype=np.float64)
+    M = len(G)
+    k = max(0, min(int(k), M))
+    lam, U = np.linalg.eigh(G)
+    lam, U = lam[::-1], U[:, ::-1]
+    Uk = U[:, :k].copy()
+    for j in range(k):
+        if Uk[int(np.argmax(np.abs(Uk[:, j]))), j] < 0:
+            Uk[:, j] = -Uk[:, j]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        explained = lam[:k] / np.trace(G)
+        participation = float(np.sum(lam) ** 2 / np.sum(lam * lam))
+    return {"eigenvalues": lam[:k].copy(), "vectors": Uk, "scores": Uk * np.sqrt(np.maximum(lam[:k], 0.0)),
+            "explained": explained, "participation": participation}
+
+
+def posterior_patterns(model_hist, dataStruct, TD_parameters, k=8, weights="volume", thin=1, xs=None, ys=None, zs=None):
+    """Which whole-volume patterns does the data leave undetermined -- the wedge trading against the slab, a depth
+    smear?  The principal components of the ensemble on the lattice ``xs`` x ``ys`` x ``zs`` (default:
+    dataStruct.xVec / yVec / zVec), a node weighing its voxel's volume (``weights`` as for ``ensemble_distances``).
+    The M x M Gram matrix of the centred samples is formed on the device (td_rasterize_gram / td_history_gram); its
+    eigen-decomposition is the host's (numpy.linalg.eigh: LAPACK's time, O(M^3), is not the device's -- 9.3 s at M = 10^4
+    beside 0.45 s for the matrix where DESIGN 4.6o measured both).  -> dict: ``eigenvalues`` [k]; ``explained`` [k] =
+    eigenvalue / trace; ``participation``; ``scores`` [M, k], one number per sample and pattern (unit eigenvector
+    times sqrt(eigenvalue), signs fixed as in ``pattern_summary``), shaped for ``posterior_covariance(series=...)``;
+    ``patterns`` [k, nx, ny, nz], the regression of zeta at every node on a score, cov / std(score): zeta per sigma of
+    the score; ``corr`` [k, nx, ny, nz]; ``score_std`` [k]; ``mean``, ``std`` [nx, ny, nz]; where every chain
+    holds at least 4 samples ``rhat``, ``ess``, ``lags`` [k], each score's split R-hat and effective
+    sample size (td_convergence_values): model-space mixing in k numbers; ``chain_of`` [M]; ``x``, ``y``, ``z``.
+    ``thin`` as for ``ensemble_distances``.  The maps come from the existing covariance call with ``series=scores``."""
+    ctx = context_for(dataStruct)  # (TD_parameters: the siblings' signature; the lattice decides everything here)
+    xv, yv, zv, shape, qx, qy, qz = _lattice(dataStruct, xs, ys, zs)
+    w = _node_weights(weights, xv, yv, zv, shape)
+    models, lens = _thinned(model_hist, thin)
+    if _on_device(models):
+        r = ctx.gram_history(models, qx, qy, qz, w, want=("gram",))
+    else:
+        r = ctx.gram([m.cells() for m in models], qx, qy, qz, w, want=("gram",))
+    out = pattern_summary(r["gram"], k)
+    del out["vectors"]
+    cov = posterior_covariance(models, dataStruct, TD_parameters, None, series=out["scores"], xs=xv, ys=yv, zs=zv)
+    sd = cov["target_std"]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["patterns"] = cov["cov"] / sd[:, None, None, None]
+    out.update(corr=cov["corr"], score_std=sd, mean=cov["mean"], std=cov["std"], x=xv, y=yv, z=zv,
+               chain_of=np.repeat(np.arange(len(lens)), lens), weight_sum=r["wsum"])
+    if out["scores"].shape[1] > 0 and min(lens) >= 4:
+        c = ctx.convergence(out["scores"], lens)
+        out.update(rhat=c["rhat"], ess=c["ess"], lags=c["lags"])
+    return out
+
+
 def posterior_predictive(model_hist, dataStruct, TD_parameters, probs=(0.05, 0.5, 0.95), bins=None, convergence=False,
                          values=False, max_lag=0):
     """Does the ensemble fit the data, ray by ray, and does it predict data it was not fitted to?  Every
