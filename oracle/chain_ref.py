@@ -1,5 +1,6 @@
 """Literal Python restatement of the rj-MCMC loop WITH the data in play --
-TEST INFRASTRUCTURE ONLY (tests/test_chain_reference.py, tests/test_gpu_chain_reference.py).
+TEST INFRASTRUCTURE ONLY (tests/test_chain_reference.py, tests/test_gpu_chain_reference.py,
+tests/test_gpu_shim_replay.py).
 
 One chain of TD_inversion_function.jl:69-288, statement by statement, so that every chain engine of
 the build (the HOST engine's host_iteration, the fourteen k_chain_run instances, the drop-in path,
@@ -39,7 +40,8 @@ What is NOT the reference's and comes from the caller, because only the build de
     rand(1)[1] is u_accept;
   * the temperature T, the build's one extension: (modeln.phi - model.phi) / 2 is divided by T.
 
-Not restated: action 5 (unreachable, :72), the checkpoint files (:41-67, :282-294) and the aliasing
+Not restated: action 5 (unreachable, :72), the checkpoint files (:41-67, :282-294; `resume=` restates what
+a loaded checkpoint means for the loop, no evaluate of a starting model, not the files) and the aliasing
 of :280 (push!(model_hist, model) pushes a reference whose action / accept fields later iterations
 overwrite at :73-74 until an acceptance rebinds `model`): `saved` holds the model of the saved
 iteration itself, as the build's copies do.
@@ -86,9 +88,14 @@ def _margin(u, alpha_raw):
     return abs(math.log(u) - math.log(alpha_raw))
 
 
-def run(ds, prm, cells, iters, draws, normal_quantile, start_iter=1):
+def run(ds, prm, cells, iters, draws, normal_quantile, start_iter=1, forward=None, resume=None):
     """`iters` iterations start_iter, start_iter + 1, ... of one chain from the model `cells` on the
     rays of `ds` (rayX, rayY, rayZ, rayL, rayU, tS, allSig as DataStruct holds them).
+    `forward` = (ev, interp) puts the caller's forward calls in the place of the C oracle's: ev(cells) ->
+    (phi, ptS, valid), interp(cells, x, y, z) -> float (tests/shim_replay.py: the loop drives the library as
+    the Julia host would); the evaluations are still counted here.  `resume` = (phi, ptS) of the model that
+    `cells` holds: a chain loaded from its checkpoint (:41-67) evaluates no starting model, and `start` is
+    `resume`.
     -> dict(steps = [Step], start = (phi, ptS) of the starting model (build_starting's evaluate,
     MCsub.jl:118), saved = the iterations pushed to model_hist (:275-288; [] without burn_in /
     keep_each), accepted / proposed = per action 1..4 (proposed: the branch was entered, i.e. not
@@ -114,8 +121,18 @@ def run(ds, prm, cells, iters, draws, normal_quantile, start_iter=1):
         """Interpolation(TD_parameters, model, [x], [y], [z])[1] (MCsub.jl:306-327)"""
         return float(interpolation(c, [x], [y], [z])[0][0])
 
+    if forward is not None:
+        forward_ev, interp = forward
+
+        def ev(c):
+            nev[0] += 1
+            return forward_ev(c)
+
     x, y, z, zeta = (np.array(a, dtype=np.float64) for a in cells)
-    phi, ptS, valid = ev((x, y, z, zeta))
+    if resume is None:
+        phi, ptS, valid = ev((x, y, z, zeta))
+    else:
+        phi, ptS = resume  # :41-67: the checkpoint's model as it was saved, no evaluate
     start = (phi, ptS)
     steps, saved = [], []
     accepted, proposed = [0] * 5, [0] * 5

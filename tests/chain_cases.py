@@ -1,5 +1,6 @@
 """The cases of tests/test_chain_reference.py (CPU: the conditions on the restatement alone) and
-tests/test_gpu_chain_reference.py (GPU: every chain engine against it), and the restatement's run of each
+tests/test_gpu_chain_reference.py (GPU: every chain engine against it; tests/test_gpu_shim_replay.py: the Julia
+shim's transliteration in its forward calls' place), and the restatement's run of each
 (oracle/chain_ref.py on the build's own uniforms, tdt_draws), computed once per process and never modified.
 
 A: synthetic_rays(24, seed=1), random_model(8, .), min_cells 5, max_cells 12, 1500 iterations, priors
@@ -70,15 +71,18 @@ def draws_of(tt, seed, chain):
     return draws
 
 
-def restate(tt, ds, p, model, iters, start_iter=1, burn_in=None, keep_each=None, debug_prior=0):
-    """oracle.chain_ref.run for the chain that td_chain_params `p` describes."""
+def restate(tt, ds, p, model, iters, start_iter=1, burn_in=None, keep_each=None, debug_prior=0, forward=None,
+            resume=None):
+    """oracle.chain_ref.run for the chain that td_chain_params `p` describes, from `model` (a Model, or the four
+    cell arrays of a Step); `forward` and `resume` as chain_ref.run takes them."""
     from oracle import chain_ref
 
     prm = chain_ref.Params((p.xmin, p.xmax, p.ymin, p.ymax, p.zmin, p.zmax), prior=p.prior, sig=p.sig,
                            zeta_scale=p.zeta_scale, max_cells=p.max_cells, min_cells=p.min_cells,
                            debug_prior=debug_prior, temperature=p.temperature, burn_in=burn_in, keep_each=keep_each)
-    return chain_ref.run(ds, prm, model.cells(), iters, draws_of(tt, p.seed, p.chain), tt.lib().tdt_normal_quantile,
-                         start_iter=start_iter)
+    cells = model.cells() if hasattr(model, "cells") else model
+    return chain_ref.run(ds, prm, cells, iters, draws_of(tt, p.seed, p.chain), tt.lib().tdt_normal_quantile,
+                         start_iter=start_iter, forward=forward, resume=resume)
 
 
 @functools.lru_cache(maxsize=None)
@@ -137,6 +141,41 @@ def history_diff(a, steps):
     if bad.size:
         return "ptS differs first at iteration %d" % steps[int(bad[0])].iter
     return None
+
+
+def steps_diff(got, want, with_ptS=True):
+    """What differs between two runs of oracle.chain_ref.run (==: iter, action, accept, outcome, nCells, phi, ptS
+    and the four cell arrays of every step, then accepted and proposed, and the starting model's phi and ptS),
+    or None.  Without `with_ptS` no ptS is compared (debug_prior = 1: evaluate computes none)."""
+    a, b = got["steps"], want["steps"]
+    if len(a) != len(b):
+        return "%d steps, %d wanted" % (len(a), len(b))
+    for s, w in zip(a, b):
+        for key in ("iter", "action", "accept", "outcome", "ncells", "phi"):
+            if getattr(s, key) != getattr(w, key):
+                return "%s differs first at iteration %d (action %d): %r, wanted %r" % (
+                    key, w.iter, w.action, getattr(s, key), getattr(w, key))
+        if with_ptS and not (s.ptS is not None and np.array_equal(s.ptS, w.ptS)):
+            return "ptS differs first at iteration %d (action %d)" % (w.iter, w.action)
+        for j, key in enumerate(("x", "y", "z", "zeta")):
+            if not np.array_equal(s.cells[j], w.cells[j]):
+                return "%sCell differs first at iteration %d (action %d)" % (key, w.iter, w.action)
+    for key in ("accepted", "proposed"):
+        if list(got[key]) != list(want[key]):
+            return "%s is %r, wanted %r" % (key, got[key], want[key])
+    if got["start"][0] != want["start"][0]:
+        return "the starting model's phi is %r, wanted %r" % (got["start"][0], want["start"][0])
+    if with_ptS and not (got["start"][1] is not None and np.array_equal(got["start"][1], want["start"][1])):
+        return "the starting model's ptS differs"
+    return None
+
+
+def window(steps, first, n):
+    """What a run resumed after steps[first - 1] (the model after iteration `first` of a run from iteration 1)
+    must give for n iterations, in the shape of oracle.chain_ref.run's result."""
+    part = steps[first:first + n]
+    acc, prop = counts(part)
+    return dict(steps=part, start=(steps[first - 1].phi, steps[first - 1].ptS), accepted=acc, proposed=prop)
 
 
 def counts(steps):
