@@ -335,7 +335,8 @@ int td_history_rasterize(td_ctx *ctx, td_history *const *hs, int64_t nh, const d
  * plot_distribution.jl:66-80.  V[k][q] is td_rasterize's value matrix (model k
  * at point q), M = nmodels; nothing but the results leaves the device.
  *   quant_out[p*nq + q] = Statistics.quantile(V[:, q], probs[p]), Julia's
- * default (alpha = beta = 1): with v = V[:, q] sorted ascending,
+ * default (alpha = beta = 1): with v = V[:, q] sorted ascending (isless:
+ * -0.0 before 0.0),
  *     aleph = M*p + (1 - p);  j = clamp(trunc(aleph), 1, max(M-1, 1));
  *     g = clamp(aleph - j, 0, 1);  a = v[j];  b = M == 1 ? v[1] : v[j+1]
  *     quantile = a + g*(b - a)                      (1-based, unfused FP64)
@@ -348,7 +349,8 @@ int td_history_rasterize(td_ctx *ctx, td_history *const *hs, int64_t nh, const d
  *   nprob 0..64 (0: no quantiles), nbins 0..4096 (0: no histogram); both 0
  * returns mean and std only.  TD_ERR_ARG, before any HIP call: want NULL, a
  * count out of range, a probability outside [0, 1] or NaN, lo/hi non-finite or
- * lo >= hi with nbins > 0, a NULL array for a non-zero count.
+ * lo >= hi with nbins > 0, a NULL array for a non-zero count.  hi - lo must be
+ * finite too (nbins > 0): (-1e308, 1e308) is refused, its w would be +inf.
  *   mean_out / std_out are td_rasterize's, bit for bit.  Columns of up to
  * 16384 models are sorted in LDS; longer ones take an exact radix select over
  * the value matrix in device memory (csrc/marginals.hip); same results.

@@ -263,10 +263,18 @@ int tdt_set_nn_method(td_ctx *ctx, int method);
  * values at probability p, the 1-based j and the weight g of v[j+1] (include/tdstar.h); needs no GPU.
  * tdt_set_marginals_method: the regime that selects the order statistics, 0 auto (resident up to
  * tdt_marginals_resident_max models), 1 resident (columns sorted in LDS; a later call with more models
- * than it holds returns TD_ERR_ARG), 2 streaming (radix select over device memory).  Same results. */
+ * than it holds returns TD_ERR_ARG), 2 streaming (radix select over device memory).  Same results.
+ * tdt_marginals_plan: the quantile kernel's launch for M models x nq nodes on num_cus compute units
+ * (td_info.num_cus) under that method with nprob probabilities, out = {resident (0 / 1), Mp, W, threads,
+ * dynamic LDS bytes}; pure host code.  Resident: a workgroup sorts a tile of W nodes x Mp keys (M rounded
+ * up to a power of two) in LDS: W = min(64, 16384 / Mp), halved while W > 8 and ceil(nq / W) < 2 num_cus;
+ * threads = Mp W / 2 within 64 .. 1024; 8 Mp W bytes.  Streaming: {0, 0, 1, 512, 2048 nprob} (a workgroup
+ * per node).  TD_ERR_ARG where a call would refuse (method 1 beyond tdt_marginals_resident_max) and for
+ * M < 1, nq < 1, num_cus < 0, nprob outside 0 .. 64. */
 int tdt_quantile_rank(int64_t M, double p, int64_t *j, double *g);
 int tdt_set_marginals_method(td_ctx *ctx, int method);
 int tdt_marginals_resident_max(td_ctx *ctx, int64_t *M);
+int tdt_marginals_plan(int64_t M, int64_t nq, int num_cus, int method, int nprob, int64_t out[5]);
 
 /* Convergence diagnostics (td_convergence_values).  tdt_convergence_plan: what the chain lengths and
  * max_lag decide (include/tdstar.h), out = {n, m, T, first row of sequence 0}, seq_start [m] (nullable)

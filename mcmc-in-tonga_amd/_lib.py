@@ -288,6 +288,7 @@ SIGNATURES = {
     "tdt_quantile_rank": (ctypes.c_int, [_i64, _d, _pi64, _pd]),
     "tdt_set_marginals_method": (ctypes.c_int, [_vp, ctypes.c_int]),
     "tdt_marginals_resident_max": (ctypes.c_int, [_vp, _pi64]),
+    "tdt_marginals_plan": (ctypes.c_int, [_i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _pi64]),
     "tdt_philox": (None, [_pu32, _pu32, _pu32]),
     "tdt_det_log": (_d, [_d]),
     "tdt_det_exp": (_d, [_d]),

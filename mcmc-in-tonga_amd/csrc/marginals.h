@@ -2,6 +2,7 @@
 // per-node quantiles (Julia's Statistics.quantile, alpha = beta = 1), per-node histograms and the
 // pooled zeta histogram of recorded samples.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #include "ctx.h"
@@ -35,6 +36,18 @@ int marg_check_bins(td_ctx *ctx, int64_t nbins, double lo, double hi, const char
 // cannot hold), for the entry points to make before they issue anything: marginals_run itself runs
 // behind their search kernels and copies.  want may be NULL.
 int marg_check_models(td_ctx *ctx, const td_marginals *want, int64_t M);
+
+// The launch of the quantile kernel for a value matrix of M models x nq nodes on num_cus compute units
+// under method (0 auto, 1 resident, 2 streaming) with nprob probabilities; pure host code.  Resident: a
+// tile of W nodes (a power of two, at most 64: the kernel's has_nan) x Mp keys (M rounded up to a power
+// of two), Mp * W <= kMargResidentMax.  Streaming: Mp 0, W 1 (a workgroup per node), the 2 nprob digit
+// histograms as lds.  false: the resident regime forced on more models than it holds.
+struct MargPlan {
+    bool resident = false;
+    int Mp = 1, W = 1, logW = 0, threads = 64;
+    size_t lds = 0;  // dynamic LDS, bytes
+};
+bool marginals_plan(int64_t M, int64_t nq, int num_cus, int method, int nprob, MargPlan *plan);
 
 // Quantiles and histograms of the device value matrix values[M][nq] (left unchanged), enqueued on
 // ctx->stream with the copies to want's host arrays; the caller synchronises.

@@ -206,7 +206,7 @@ void quantile_rank(int64_t M, double p, int64_t *j, double *g) {
 int marg_check_bins(td_ctx *ctx, int64_t nbins, double lo, double hi, const char *who) {
     const std::string w(who);
     if (nbins < 0 || nbins > kMargMaxBins) return set_err(ctx, TD_ERR_ARG, w + ": nbins must be 0..4096");
-    if (nbins > 0 && !(std::isfinite(lo) && std::isfinite(hi) && lo < hi))
+    if (nbins > 0 && !(std::isfinite(lo) && std::isfinite(hi) && lo < hi && std::isfinite(hi - lo)))
         return set_err(ctx, TD_ERR_ARG, w + ": need finite lo < hi");
     return TD_OK;
 }
@@ -223,6 +223,30 @@ int marg_check_want(td_ctx *ctx, const td_marginals *want, const char *who) {
     if (int rc = marg_check_bins(ctx, want->nbins, want->lo, want->hi, who)) return rc;
     if (want->nbins > 0 && !want->hist_out) return set_err(ctx, TD_ERR_ARG, w + ": hist_out must be given for nbins > 0");
     return TD_OK;
+}
+
+bool marginals_plan(int64_t M, int64_t nq, int num_cus, int method, int nprob, MargPlan *plan) {
+    MargPlan p;
+    p.resident = method == 1 || (method == 0 && M <= kMargResidentMax);
+    if (p.resident) {
+        if (M > kMargResidentMax) return false;
+        while (p.Mp < M) p.Mp <<= 1;
+        // the widest tile the LDS holds, narrowed (down to 8 nodes: 64-byte rows) until the tiles
+        // are two per CU
+        p.W = (int)std::min<int64_t>(64, kMargResidentMax / p.Mp);
+        while (p.W > 8 && (nq + p.W - 1) / p.W < 2 * (int64_t)num_cus) p.W >>= 1;
+        while ((1 << p.logW) < p.W) ++p.logW;
+        const int npairs = (p.Mp / 2) * p.W;
+        p.threads = 64;
+        while (p.threads < npairs && p.threads < 1024) p.threads <<= 1;
+        p.lds = sizeof(unsigned long long) * (size_t)p.Mp * p.W;
+    } else {
+        p.Mp = 0;
+        p.threads = kStreamThreads;
+        p.lds = sizeof(int) * 256 * 2 * (size_t)nprob;
+    }
+    *plan = p;
+    return true;
 }
 
 int marg_check_models(td_ctx *ctx, const td_marginals *want, int64_t M) {
@@ -255,29 +279,18 @@ int marginals_run(td_ctx *ctx, const double *values, int64_t M, int64_t nq, cons
             hp->jb[i] = M == 1 ? 0 : (int)j;
         }
         TD_HIP(ctx, hipMemcpyAsync(dpar, hp, par_b, hipMemcpyHostToDevice, ctx->stream));
-        const bool resident = ctx->marg_method == 1 || (ctx->marg_method == 0 && M <= kMargResidentMax);
+        MargPlan plan;
+        if (!marginals_plan(M, nq, ctx->num_cus, ctx->marg_method, nprob, &plan))
+            return set_err(ctx, TD_ERR_ARG, "td_marginals: the resident regime cannot hold this many models");
         hipEvent_t t0 = tm ? tm->begin(ctx->stream) : nullptr;
-        if (resident) {
-            int Mp = 1;
-            while (Mp < M) Mp <<= 1;
-            // the widest tile the LDS holds, narrowed (down to 8 nodes: 64-byte rows) until the tiles
-            // are two per CU
-            int W = (int)std::min<int64_t>(64, kMargResidentMax / Mp);
-            while (W > 8 && (nq + W - 1) / W < 2 * (int64_t)ctx->num_cus) W >>= 1;
-            int logW = 0;
-            while ((1 << logW) < W) ++logW;
-            const int npairs = (Mp / 2) * W;
-            int nt = 64;
-            while (nt < npairs && nt < 1024) nt <<= 1;
-            const size_t lds = sizeof(unsigned long long) * (size_t)Mp * W;
-            if (int rc = allow_lds(ctx, (const void *)k_node_quantiles_resident, lds)) return rc;
-            hipLaunchKernelGGL(k_node_quantiles_resident, dim3((unsigned)((nq + W - 1) / W)), dim3(nt), lds, ctx->stream,
-                               values, (int)M, (int)nq, Mp, logW, dpar, nprob, dquant);
+        if (plan.resident) {
+            if (int rc = allow_lds(ctx, (const void *)k_node_quantiles_resident, plan.lds)) return rc;
+            hipLaunchKernelGGL(k_node_quantiles_resident, dim3((unsigned)((nq + plan.W - 1) / plan.W)), dim3(plan.threads),
+                               plan.lds, ctx->stream, values, (int)M, (int)nq, plan.Mp, plan.logW, dpar, nprob, dquant);
         } else {
-            const size_t lds = sizeof(int) * 256 * 2 * (size_t)nprob;
-            if (int rc = allow_lds(ctx, (const void *)k_node_quantiles_stream, lds)) return rc;
-            hipLaunchKernelGGL(k_node_quantiles_stream, dim3((unsigned)nq), dim3(kStreamThreads), lds, ctx->stream, values,
-                               (int)M, (int)nq, dpar, nprob, dquant);
+            if (int rc = allow_lds(ctx, (const void *)k_node_quantiles_stream, plan.lds)) return rc;
+            hipLaunchKernelGGL(k_node_quantiles_stream, dim3((unsigned)nq), dim3(plan.threads), plan.lds, ctx->stream,
+                               values, (int)M, (int)nq, dpar, nprob, dquant);
         }
         if (tm) tm->end("raster_quantile", t0, ctx->stream);
         TD_HIP(ctx, hipGetLastError());
@@ -344,6 +357,20 @@ extern "C" int td_history_zeta_hist(td_ctx *ctx, td_history *const *hs, int64_t 
 extern "C" int tdt_quantile_rank(int64_t M, double p, int64_t *j, double *g) {
     if (M < 1 || !(p >= 0.0 && p <= 1.0) || !j || !g) return TD_ERR_ARG;
     quantile_rank(M, p, j, g);
+    return TD_OK;
+}
+
+extern "C" int tdt_marginals_plan(int64_t M, int64_t nq, int num_cus, int method, int nprob, int64_t out[5]) {
+    if (M < 1 || M > INT64_C(0x7fffffff) || nq < 1 || num_cus < 0 || method < 0 || method > 2 || nprob < 0 ||
+        nprob > kMargMaxProbs || !out)
+        return TD_ERR_ARG;
+    MargPlan p;
+    if (!marginals_plan(M, nq, num_cus, method, nprob, &p)) return TD_ERR_ARG;
+    out[0] = p.resident ? 1 : 0;
+    out[1] = p.Mp;
+    out[2] = p.W;
+    out[3] = p.threads;
+    out[4] = (int64_t)p.lds;
     return TD_OK;
 }
 

@@ -190,6 +190,15 @@ class TdContext:
         return m.value
 
     @staticmethod
+    def marginals_plan(nmodels, nq, num_cus, method=0, nprob=1):
+        """(resident, Mp, W, threads, dynamic LDS bytes) of the quantile kernel ``marginals`` launches for
+        ``nmodels`` x ``nq`` values on ``num_cus`` compute units under ``method``; needs no GPU."""
+        out = np.zeros(5, dtype=np.int64)
+        check(lib().tdt_marginals_plan(int(nmodels), int(nq), int(num_cus), int(method), int(nprob),
+                                       ptr(out, _lib._pi64)))
+        return bool(out[0]), int(out[1]), int(out[2]), int(out[3]), int(out[4])
+
+    @staticmethod
     def _marginals_want(nq, probs, bins):
         """(td_marginals, the arrays it points to, quantiles or None, hist or None)"""
         probs = f64(np.ravel(np.asarray(probs, dtype=np.float64)))

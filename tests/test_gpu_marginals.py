@@ -4,6 +4,7 @@ formula restated (np.quantile rounds differently), and floor((v - lo) / w) for t
 import numpy as np
 import pytest
 
+from marginals_ref import rank, ref_hist, ref_quantiles, ref_slots  # noqa: F401 (test_gpu_predict imports them here)
 from oracle import oracle_np
 
 pytestmark = pytest.mark.gpu
@@ -14,45 +15,6 @@ PROBS = (0.0, 0.025, 0.05, 1 / 3, 0.5, 0.95, 1.0)
 @pytest.fixture(scope="module")
 def ctx(tt, ds):
     return tt.TdContext.from_datastruct(ds)
-
-
-def rank(M, p):
-    aleph = M * p + (1 - p)
-    j = min(max(int(np.trunc(aleph)), 1), max(M - 1, 1))
-    g = min(max(aleph - j, 0.0), 1.0)
-    return j, g
-
-
-def ref_quantiles(V, probs):
-    M = len(V)
-    S = np.sort(V, axis=0)  # (NaN last)
-    out = np.empty((len(probs), V.shape[1]))
-    for i, p in enumerate(probs):
-        j, g = rank(M, p)
-        a = S[j - 1]
-        b = S[0] if M == 1 else S[j]
-        with np.errstate(invalid="ignore"):
-            out[i] = a + g * (b - a)
-    out[:, np.isnan(V).any(axis=0)] = np.nan
-    return out
-
-
-def ref_slots(v, bins):
-    nbins, lo, hi = bins
-    w = (hi - lo) / nbins
-    v = np.asarray(v, dtype=np.float64)
-    with np.errstate(invalid="ignore"):
-        b = np.floor((v - lo) / w)
-        s = 1 + np.minimum(np.where(np.isnan(b), 0, b), nbins - 1).astype(np.int64)
-        s[v < lo] = 0
-        s[v >= hi] = nbins + 1
-    s[np.isnan(v)] = nbins + 2
-    return s
-
-
-def ref_hist(V, bins):
-    s = ref_slots(V, bins)
-    return np.array([np.bincount(s[:, q], minlength=bins[0] + 3) for q in range(V.shape[1])], dtype=np.int64)
 
 
 def check(ctx, models, qx, qy, qz, probs=PROBS, bins=(25, 0.0, 50.0), ref=None):
